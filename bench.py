@@ -1,13 +1,15 @@
 #!/usr/bin/env python
 """bench.py -- WS3D hot-path benchmark on MI355X (driver contract: one JSON line on rank 0).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|s2|t1] [--batch B]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload c3|c2|c5|s2|t1] [--batch B] [--full] [--dump-outputs DIR]
 
 With no flags it measures BASELINE.json's headline: workload **c3** = configs[2], the full Stage-1 RPN
-forward + proposal NMS + roipool3d at batch 8 scenes/GPU (`value` = throughput mode, `latency_mode` =
-one batch in flight, both in the same line), and -- outside the timed region -- the **c2** block
-(configs[1]: FPS 16384->4096 + fused ball_query/group, the "FPS+group HBM GB/s" half of the metric)
-with the `roofline` of the path's dominant kernel.
+forward + proposal NMS + roipool3d at batch 8 scenes/GPU (`value` = throughput mode).  A plain run sets up,
+warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last timed step
+computed (step_outputs / dump_outputs).  With --full, and outside the timed region, it goes on to
+`latency_mode` (one batch in flight), the **c2** block (configs[1]: FPS 16384->4096 + fused
+ball_query/group, the "FPS+group HBM GB/s" half of the metric), the `roofline` of the path's dominant
+kernel and the CPU baselines.
 
 N > 1 runs one rank per GPU over RCCL, either way of starting it: under the driver's ``python -m torch.distributed.run
 --nproc-per-node N ... bench.py --gpus N`` (RANK / WORLD_SIZE from the environment), or as plain ``python bench.py --gpus N``,
@@ -27,7 +29,7 @@ already resident in HBM:
        128 channels
   t1 : one Stage-1 RPN training iteration, batch 8 (bench_t1.py)
 
-Extra objects on the JSON line (tier contract): "roofline" for the dominant kernel (FPS:
+Extra objects on the JSON line with --full (tier contract): "roofline" for the dominant kernel (FPS:
 algorithmic bytes A_model = (M-1)*N*12 + M*4 per scene) with the per-launch
 duration measured live with HIP events on the launch stream, and "cpu_baseline" (the CPU
 oracle port, OpenMP over scenes, timed on this box's host cores on a bounded sample).
@@ -231,15 +233,16 @@ def compact_line(out, detail_path):
     for k in ("launch", "exchange", "hw_queues", "pipeline_depth", "untimed_before_clock", "m_points", "nsample", "radius", "proposals", "channels", "sampled"):
         if k in cfg and not isinstance(cfg[k], (dict, list)):
             line["config"][k] = _short(cfg[k], 120) if isinstance(cfg[k], str) else cfg[k]
-    roof = dict(out["roofline"])
-    for k in ("note", "frac_is"):
-        if k in roof:
-            roof[k] = _short(roof[k], 120)
-    roof.pop("note", None)
-    roof["kernel"] = _short(roof.get("kernel", roof.get("measured_in", "")), 160) if "kernel" in roof else None
-    if roof["kernel"] is None:
-        roof.pop("kernel")
-    line["roofline"] = roof
+    if "roofline" in out:                           # (--full: the per-kernel table it is taken from runs after the timed region)
+        roof = dict(out["roofline"])
+        for k in ("note", "frac_is"):
+            if k in roof:
+                roof[k] = _short(roof[k], 120)
+        roof.pop("note", None)
+        roof["kernel"] = _short(roof.get("kernel", roof.get("measured_in", "")), 160) if "kernel" in roof else None
+        if roof["kernel"] is None:
+            roof.pop("kernel")
+        line["roofline"] = roof
     if "cpu_baseline" in out:
         cb = out["cpu_baseline"]
         line["cpu_baseline"] = {k: (_short(v, 280) if isinstance(v, str) else v) for k, v in cb.items() if k not in ("host", "ms_per_scene_by_part", "search_only")}
@@ -287,8 +290,73 @@ def compact_line(out, detail_path):
     if len(text) > LINE_BUDGET:                     # never lose the line to its own size again: drop the optional scalars first
         for k in [k for k in line if k.startswith(("c2_", "latency_ms_", "value_all"))]:
             line.pop(k)
-        line["roofline"].pop("dominant_kernel", None)
+        line.get("roofline", {}).pop("dominant_kernel", None)
     return line
+
+
+DUMP_BUDGET = 64 << 20      # bytes of all --dump-outputs arrays together
+DUMP_SAMPLE = 1 << 20       # elements kept of an array too large to write whole: a fixed, seeded sample of its flat indices
+
+
+def step_outputs(wl):
+    """-> {name: device tensor}: what a caller of the timed path received from its LAST step.  Read right after the timed region,
+    before anything else reuses the buffers.  Entries that the path leaves undefined are masked: rows of empty RoIs in `pooled`
+    (never written, by contract) -> 0, NMS keep slots past `num` -> -1."""
+    name = wl.name
+    if name.startswith("c3"):
+        rpn, boxes, scores, count, pooled, empty, gathered = wl.last
+        out = {k: rpn[k] for k in ("rpn_cls", "rpn_reg", "backbone_xyz", "backbone_features")}
+        out.update(boxes=boxes, scores=scores, count=count, pooled=pooled, empty=empty)
+        if wl.world > 1:
+            out.update(gathered=gathered[0], gathered_count=gathered[1])
+        return out
+    if name.startswith("c2"):
+        return {"idx": wl.idx, "new_xyz": wl.new_xyz, "nbr": wl.nbr, "grouped": wl.grouped}
+    if name.startswith("c5"):
+        keep = wl.keep.masked_fill(torch.arange(wl.keep.size(1), device=wl.keep.device)[None, :] >= wl.num[:, None].long(), -1)
+        return {"pooled": wl.pooled, "empty": wl.empty, "keep": keep, "num": wl.num}
+    if name.startswith("s2"):
+        return {"idx1": wl.idx1, "new_xyz1": wl.new1, "nbr1": wl.nbr1, "grouped1": wl.out1, "idx2": wl.idx2, "new_xyz2": wl.new2,
+                "nbr2": wl.nbr2, "grouped2": wl.out2, "group_all": wl.out3}
+    if name.startswith("t1"):
+        return {k: torch.tensor(float(v), dtype=torch.float64) for k, v in wl.last.items()
+                if isinstance(v, (int, float)) or (torch.is_tensor(v) and v.numel() == 1)}
+    if hasattr(wl, "ops"):
+        out = {"gathered": wl.gathered, "interp": wl.interp, "dist2": wl.dist2, "nn_idx": wl.nn_idx, "overlap": wl.overlap}
+        out.update({"grouped_c%d_ns%d" % k: v for k, v in wl.grouped.items()})
+        out.update({"ball_query_ns%d" % k: v for k, v in wl.bq.items()})
+        return out
+    raise SystemExit("bench.py: --dump-outputs knows no outputs of workload %s" % name)
+
+
+def dump_outputs(wl, folder):
+    """--dump-outputs: every output of the last timed step as <folder>/<name>.npy (float32; integers as float64), an array of more
+    than DUMP_SAMPLE elements as <folder>/<name>_sample.npy = the elements at DUMP_SAMPLE flat indices drawn once from a fixed seed"""
+    torch.cuda.synchronize()
+    outs = step_outputs(wl)
+    os.makedirs(folder, exist_ok=True)
+    total = 0
+    for name, t in outs.items():
+        flat = t.detach().reshape(-1)
+        fname = name
+        if flat.numel() > DUMP_SAMPLE:
+            pick = np.sort(np.random.default_rng(0).choice(flat.numel(), DUMP_SAMPLE, replace=False))
+            pick_t = torch.from_numpy(pick).to(flat.device)
+            flat = flat[pick_t]
+            if name == "pooled" and "empty" in outs:           # rows of empty RoIs are never written: zero them
+                row_len = t[0, 0].numel()
+                flat = flat.masked_fill(outs["empty"].reshape(-1)[pick_t // row_len] != 0, 0)
+            fname = name + "_sample"
+        elif name == "pooled" and "empty" in outs:
+            flat = (t.masked_fill((outs["empty"] != 0)[:, :, None, None], 0)).reshape(-1)
+        a = flat.cpu().numpy()
+        a = a.astype(np.float32 if a.dtype.kind == "f" and a.itemsize <= 4 else np.float64)
+        if flat.numel() == t.numel():
+            a = a.reshape(tuple(t.shape))
+        total += a.nbytes
+        if total > DUMP_BUDGET:
+            raise SystemExit("bench.py: --dump-outputs would write more than %d bytes" % DUMP_BUDGET)
+        np.save(os.path.join(folder, fname + ".npy"), a)
 
 
 def c2_block(batch, rank, kind, steps=10, warmup=2):
@@ -419,6 +487,13 @@ def main():
                          "collective library's own hardware queues: beyond 23 queues per process the runtime time-slices, DESIGN.md 5.6)")
     ap.add_argument("--settle", type=float, default=1.0,
                     help="c3, graph mode: seconds of untimed replays between the priming replays and the timed region (the device's sustained state; 0: none)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what lies beside the headline, after the timed region: latency mode, steady state, the per-kernel table and "
+                         "roofline, list_fill, the c3 side runs, the c2 block and the CPU baselines.  Without it a run sets up, warms up, times "
+                         "--steps steps and prints the line (contract keys and config)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step to DIR/<name>.npy (float32 / float64; arrays of more than "
+                         "%d elements as a fixed, seeded sample DIR/<name>_sample.npy; %d MB at most)" % (DUMP_SAMPLE, DUMP_BUDGET >> 20))
     args = ap.parse_args()
     if args.steps is None:
         args.steps = 80 if args.workload == "c3" else 40
@@ -471,11 +546,13 @@ def main():
     dt = max_over_ranks(time.perf_counter() - t0, world)
 
     # ---- everything below is outside the timed region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(wl, args.dump_outputs)
     total_scenes = wl.scenes() * world * args.steps
     value = total_scenes / dt
     ms_per_step = dt / args.steps * 1e3
     latency = None
-    if hasattr(wl, "latency_mode"):
+    if args.full and hasattr(wl, "latency_mode"):
         # the same step with ONE batch in flight (submit, exchange, wait): what a caller that needs the
         # proposals of this batch before it submits the next one sees
         lat, lat_detail = wl.latency_mode(n=20)
@@ -484,7 +561,7 @@ def main():
                    "unit": getattr(wl, "unit", "scenes/s"), "batches_timed": 20, "statistic": "median",
                    "launch": min(lat_detail, key=lat_detail.get)[:-3], "rank0_ms_by_launch": lat_detail}
     steady = None
-    if use_graph and args.workload == "c3" and args.steps >= 20 and not args.no_side_runs:
+    if args.full and use_graph and args.workload == "c3" and args.steps >= 20 and not args.no_side_runs:
         # the same replay loop once more over 160 steps (eight rounds over the slots), OUTSIDE the contract's timed region: the
         # driver's flags time one pipeline fill (20 steps at depth 20); this says what the loop sustains
         barrier_sync(world)
@@ -494,7 +571,7 @@ def main():
         barrier_sync(world)
         dt1 = max_over_ranks(time.perf_counter() - t1, world)
         steady = {"value": wl.scenes() * world * 160 / dt1, "ms_per_step": dt1 / 160 * 1e3, "steps": 160}
-    if use_graph:
+    if args.full and use_graph:
         # per-kernel HIP-event table from EAGER steps (events cannot be recorded inside a graph): >= 50 of them at the driver's flags
         # (median + p10 / p90 over >= 50 iterations); `value` above is the graph-replay throughput
         for _ in range(50 if args.steps >= 20 else min(args.steps, 5)):
@@ -502,20 +579,20 @@ def main():
         torch.cuda.synchronize()
     if os.environ.get("WS3D_BENCH_DUMP") and hasattr(wl, "dump"):
         wl.dump(os.environ["WS3D_BENCH_DUMP"])
-    kernels = finish_kernel_rows(wl.kernel_table(), wl.scenes(), getattr(wl, 'kind', args.kind)) if rank == 0 else None
+    kernels = finish_kernel_rows(wl.kernel_table(), wl.scenes(), getattr(wl, 'kind', args.kind)) if (args.full and rank == 0) else None
     side = {}
-    if args.workload == "c3" and rank == 0:
+    if args.full and args.workload == "c3" and rank == 0:
         # distinct pairs per ball-query scale on the timed batch: what the matrix roofline of the step is counted from
         side["list_fill"] = {"generator": wl.kind, "scales": wl.list_fill()}
-    if args.workload == "c3" and world == 1 and not args.no_side_runs and use_graph:
+    if args.full and args.workload == "c3" and world == 1 and not args.no_side_runs and use_graph:
         side.update(c3_side_runs(wl, args, value, latency))
     c2wl = c2blk = None
-    if args.workload == "c3" and args.c2_batch > 0:
+    if args.full and args.workload == "c3" and args.c2_batch > 0:
         c2wl, c2blk = c2_block(args.c2_batch, rank, args.kind)
     barrier_sync(world)
 
     if rank == 0:
-        dom = max((k for k in kernels if k["launches_per_step"] > 0), key=lambda k: k["ms_per_step"])
+        dom = max((k for k in kernels if k["launches_per_step"] > 0), key=lambda k: k["ms_per_step"]) if kernels else None
         per_gpu = value / world
         out = {
             "metric": getattr(wl, "metric", HEADLINE_METRIC), "value": value, "unit": getattr(wl, "unit", "scenes/s"),
@@ -546,11 +623,11 @@ def main():
             c2dom = max(c2blk["kernels"], key=lambda k: k["ms_per_step"])
             c2blk["roofline"] = roofline_of(c2dom, "c2 block of this run (batch %d per launch)" % c2blk["batch_per_gpu"])
             out["c2"] = c2blk
-        if args.workload == "ops":
+        if kernels and args.workload == "ops":
             # the copy operator FURTHEST from its HBM roof: SURVEY 8(d) applies the 40 % target to each of them literally
             dom = min((k for k in kernels if k.get("bound") == "hbm"), key=lambda k: k["frac_of_8TBps"])
             out["ops_hbm_frac"] = {k["name"].split(" ")[0]: k["frac_of_8TBps"] for k in kernels if k.get("bound") == "hbm"}
-        if args.workload != "c3":
+        if kernels and args.workload != "c3":
             out["roofline"] = roofline_of(dom, "the timed region of this line (HIP events on the launch stream)")
         out.update(side)
         if "list_fill" in out and "throughput_mode" in out and hasattr(wl, "cfg"):
@@ -567,10 +644,11 @@ def main():
                 ar = bench_c3.matrix_work(wl.cfg, out["list_fill"]["scales"], wl.scenes(), compact=False)["gflop_per_batch"]
                 mw["all_rows"] = {"gflop_per_batch": ar, "achieved": ar / out["all_rows"]["ms_per_batch"], "frac": ar / out["all_rows"]["ms_per_batch"] / bench_c3.FP32_MFMA_PEAK_TFLOPS}
             out["throughput_mode"]["matrix_roofline"] = mw
-        if args.workload == "c3":
+        if kernels and args.workload == "c3":
             out["roofline"] = c3_step_roofline(out, kernels, wl, getattr(wl, "kind", args.kind))
-        out.update({"kernels": kernels, "step_ms_percentiles": step_percentiles(wl), "path_gbps_per_gpu": wl.path_gbps(per_gpu)})
-        if not args.no_cpu_baseline and world == 1:
+        if kernels:
+            out.update({"kernels": kernels, "step_ms_percentiles": step_percentiles(wl), "path_gbps_per_gpu": wl.path_gbps(per_gpu)})
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"] = wl.cpu_baseline(min_seconds=args.cpu_baseline_seconds)
                 if c2wl is not None:

@@ -7,7 +7,7 @@ KIND=${1:-hdl64}
 export TMPDIR=/tmp WS3D_TUNE_GEMMS=0
 for S in 20 60; do
   rm -rf /tmp/prof_lps_$S
-  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_lps_$S -o l -- python bench.py --kind $KIND --steps $S --warmup 2 --no-side-runs --no-cpu-baseline --c2-batch 0 > /dev/null 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -d /tmp/prof_lps_$S -o l -- python bench.py --full --kind $KIND --steps $S --warmup 2 --no-side-runs --no-cpu-baseline --c2-batch 0 > /dev/null 2>&1
   python scripts/rocpd_stats.py $(find /tmp/prof_lps_$S -name "*.db" | head -1) > /tmp/lps_$S.csv
 done
 python - <<'P'

@@ -1,6 +1,6 @@
 """HBM traffic of ONE eager Stage-1 step (c3, batch 8) per launch family of bench_c3.py's kernel table, from two separate
 rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; kernel trace only, as MI355X_MICROARCH.md prescribes) over
-``python bench.py --workload c3 --pipeline-depth 1 --no-graph --c2-batch 0 --no-cpu-baseline --no-side-runs``:
+``python bench.py --full --workload c3 --pipeline-depth 1 --no-graph --c2-batch 0 --no-cpu-baseline --no-side-runs``:
 
     python scripts/pmc_traffic_c3.py <fetch.db> <write.db> <out.json> <generator> <batch>
 

@@ -7,7 +7,7 @@ OUT=${1:-gpurun_out/pmc_valu}; mkdir -p $OUT; export TMPDIR=/tmp
 for b in 512 256; do
   for c in SQ_INSTS_VALU SQ_INSTS_SALU SQ_WAVES GRBM_GUI_ACTIVE SQ_BUSY_CYCLES; do
     rm -rf /tmp/pv_$c
-    (cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace -d /tmp/pv_$c -o pv -- python $OLDPWD/bench.py --workload c2 --batch $b --steps 3 --warmup 1 --no-cpu-baseline > $OLDPWD/$OUT/log_${b}_$c.txt 2>&1)
+    (cd /tmp && timeout 600 rocprofv3 --pmc $c --kernel-trace -d /tmp/pv_$c -o pv -- python $OLDPWD/bench.py --full --workload c2 --batch $b --steps 3 --warmup 1 --no-cpu-baseline > $OLDPWD/$OUT/log_${b}_$c.txt 2>&1)
     python - "$(find /tmp/pv_$c -name '*.db' | head -1)" $c $b >> $OUT/valu_counters.txt <<'PY'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1]); c, b = sys.argv[2], sys.argv[3]

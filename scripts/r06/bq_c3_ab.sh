@@ -9,7 +9,7 @@ timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_golden.py tests
 run() {
   echo "== $1" | tee -a $out/ab.txt
   python scripts/ubench/bq_pairs_levels.py 2>&1 | grep -v amdgpu.ids | tee -a $out/ab.txt
-  python bench.py --full-line --no-cpu-baseline --no-side-runs --c2-batch 0 --steps 160 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c3 160 steps: %.1f scenes/s  %.4f ms/step' % (d['value'], d['ms_per_step']))" | tee -a $out/ab.txt
+  python bench.py --full --full-line --no-cpu-baseline --no-side-runs --c2-batch 0 --steps 160 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c3 160 steps: %.1f scenes/s  %.4f ms/step' % (d['value'], d['ms_per_step']))" | tee -a $out/ab.txt
 }
 : > $out/ab.txt
 run default

@@ -4,7 +4,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 OUT=${1:-gpurun_out}; export TMPDIR=/tmp
 rm -rf /tmp/pmc_bqe
-(cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --kernel-trace -d /tmp/pmc_bqe -o p -- python $OLDPWD/bench.py --workload c2 --batch 512 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
+(cd /tmp && timeout 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_INST_ANY --kernel-trace -d /tmp/pmc_bqe -o p -- python $OLDPWD/bench.py --full --workload c2 --batch 512 --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1)
 python - "$(find /tmp/pmc_bqe -name '*.db' | head -1)" <<'PY'
 import sqlite3, sys
 db = sqlite3.connect(sys.argv[1])

@@ -11,13 +11,13 @@ mkdir -p $out
 run() {
   echo "== $1" | tee -a $out/ab.txt
   rm -rf /tmp/gpc_prof
-  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/gpc_prof -o p -- python bench.py --workload c3 --steps 10 --warmup 3 --no-cpu-baseline --pipeline-depth 1 --no-graph --c2-batch 0 --no-side-runs > $out/prof.log 2>&1
+  timeout 300 rocprofv3 --kernel-trace --stats -d /tmp/gpc_prof -o p -- python bench.py --full --workload c3 --steps 10 --warmup 3 --no-cpu-baseline --pipeline-depth 1 --no-graph --c2-batch 0 --no-side-runs > $out/prof.log 2>&1
   python scripts/rocpd_stats.py "$(find /tmp/gpc_prof -name '*.db' | head -1)" 2>/dev/null | python -c "
 import csv, sys
 for r in csv.reader(sys.stdin):
     if len(r) > 3 and any(k in r[0] for k in ('gemm_pool_compact', 'pgather_gemm2_compact', 'interp_gemm_big', 'chain_mlp3')):
         print('  %-60s calls %5s  avg %9.1f ns' % (r[0][:60], r[1], float(r[3])))" | tee -a $out/ab.txt
-  python bench.py --full-line --no-cpu-baseline --no-side-runs --c2-batch 0 --steps 160 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c3 160 steps: %.1f scenes/s  %.4f ms/step' % (d['value'], d['ms_per_step']))" | tee -a $out/ab.txt
+  python bench.py --full --full-line --no-cpu-baseline --no-side-runs --c2-batch 0 --steps 160 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('c3 160 steps: %.1f scenes/s  %.4f ms/step' % (d['value'], d['ms_per_step']))" | tee -a $out/ab.txt
 }
 run default
 for v in "$@"; do

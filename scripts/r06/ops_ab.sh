@@ -6,7 +6,7 @@ timeout 600 python -m pytest tests/test_gpu_parity.py -x -q -k "group_points_wit
 for b in 8 256; do
   for v in new old; do
     if [ $v = old ]; then export WS3D_GROUP_NO_LDS=1 WS3D_TI_NO_WIDE=1; else unset WS3D_GROUP_NO_LDS WS3D_TI_NO_WIDE; fi
-    timeout 600 python bench.py --workload ops --batch $b --steps 40 --warmup 3 --no-cpu-baseline --detail $OUT/ops_${v}_b$b.json 2>/dev/null > /dev/null
+    timeout 600 python bench.py --full --workload ops --batch $b --steps 40 --warmup 3 --no-cpu-baseline --detail $OUT/ops_${v}_b$b.json 2>/dev/null > /dev/null
     python - $OUT/ops_${v}_b$b.json $v $b <<'PY' | tee -a $OUT/summary.txt
 import json, sys
 d = json.load(open(sys.argv[1]))

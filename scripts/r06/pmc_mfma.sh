@@ -10,7 +10,7 @@ P3="GRBM_GUI_ACTIVE SQ_INSTS_SMEM SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_MISC SQ_LDS
 i=0
 for P in "$P1" "$P2" "$P3"; do
   i=$((i+1)); rm -rf /tmp/pm_$i
-  (cd /tmp && timeout 400 rocprofv3 --pmc $P --kernel-trace -d /tmp/pm_$i -o pm -- python $REPO/bench.py --workload c3 --pipeline-depth 1 --no-graph --c2-batch 0 --steps 3 --warmup 2 --no-cpu-baseline --no-side-runs > $REPO/$OUT/log_$i.txt 2>&1)
+  (cd /tmp && timeout 400 rocprofv3 --pmc $P --kernel-trace -d /tmp/pm_$i -o pm -- python $REPO/bench.py --full --workload c3 --pipeline-depth 1 --no-graph --c2-batch 0 --steps 3 --warmup 2 --no-cpu-baseline --no-side-runs > $REPO/$OUT/log_$i.txt 2>&1)
   python $REPO/scripts/r06/pmc_mfma_sum.py "$(find /tmp/pm_$i -name '*.db' | head -1)" >> $OUT/counters.txt 2>&1
 done
 cat $OUT/counters.txt

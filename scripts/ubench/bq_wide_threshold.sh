@@ -10,7 +10,7 @@ for rep in 1 2; do
 for lib in default wide; do
   if [ $lib = wide ]; then export WS3D_HIP_LIB=/tmp/libws3d_bqwide.so; else unset WS3D_HIP_LIB; fi
   for kind in hdl64 lidar; do
-  python bench.py --workload c2 --kind $kind --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --workload c2 --kind $kind --no-cpu-baseline 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.readlines()[-1]); k = d['kernels']
 print('$lib $kind c2 512 scenes: %.0f scenes/s, sampling %.3f ms, binning + query + group %.3f ms = %.3f of 8 TB/s' % (d['value'], k[0]['ms_per_step'], k[1]['ms_per_step'], k[1]['frac_of_8TBps']))"

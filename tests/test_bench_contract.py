@@ -54,7 +54,7 @@ def run_bench(*flags, detail=None):
 def test_default_line_is_the_baseline_headline(tmp_path):
     """no --workload: BASELINE.json's metric on configs[2] (c3) with latency + throughput modes and the c2 block in the record;
     the LINE is compact, and its roofline describes the line's own timed region (the c3 step), not the c2 launch"""
-    line, out = run_bench("--cpu-baseline-seconds", "1", "--c2-batch", "64", "--pipeline-depth", "3", detail=tmp_path / "detail.json")
+    line, out = run_bench("--full", "--cpu-baseline-seconds", "1", "--c2-batch", "64", "--pipeline-depth", "3", detail=tmp_path / "detail.json")
     assert KEYS | {"cpu_baseline"} <= set(line), KEYS - set(line)
     lr = line["roofline"]
     assert {"bound", "achieved", "peak", "unit", "frac", "traffic", "measured_in"} <= set(lr)
@@ -100,7 +100,7 @@ def test_default_line_is_the_baseline_headline(tmp_path):
                                    ("--workload", "c5", "--no-cpu-baseline"), ("--workload", "s2", "--batch", "64", "--no-cpu-baseline"),
                                    ("--workload", "t1", "--no-cpu-baseline")])
 def test_bench_line_follows_the_contract(flags):
-    out = run_bench(*flags)
+    out = run_bench("--full", *flags)
     assert KEYS <= set(out), KEYS - set(out)
     assert out["n_gpus"] == 1 and out["steps"] == 2 and out["warmup"] == 1 and out["higher_is_better"] is True
     assert out["scaling"] == "weak" and out["vs_baseline"] is None and out["dtype"] == "f32" and "synthetic" in out["data"]
@@ -117,6 +117,51 @@ def test_bench_line_follows_the_contract(flags):
         cpu = out["cpu_baseline"]
         assert {"value", "unit", "cores", "kind", "sample"} <= set(cpu), cpu
         assert cpu["kind"] in ("port", "reference") and cpu["value"] > 0 and cpu.get("gpu_matches_oracle_on_sample", True)
+
+
+def test_plain_run_times_the_steps_and_dumps_the_last_one(tmp_path, monkeypatch):
+    """no --full: the contract keys of the headline for exactly --steps timed steps, none of the extras; --dump-outputs writes what
+    the last timed step computed (float32 / float64, 64 MB at most), and a second run on the same arguments writes the same arrays
+    (with the library's heuristic GEMM solutions, which are the same in every process)"""
+    monkeypatch.setenv("WS3D_TUNE_GEMMS", "0")
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("out%d" % k)
+        line = run_bench("--pipeline-depth", "3", "--dump-outputs", str(d))
+        assert (KEYS - {"roofline"}) <= set(line), KEYS - set(line)
+        assert line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert line["value"] == pytest.approx(line["config"]["batch_per_gpu"] * 1e3 / line["ms_per_step"], rel=1e-4)
+        assert not {"roofline", "cpu_baseline", "latency_ms", "c2_batch", "value_lidar", "value_steady"} & set(line)
+        files = sorted(os.listdir(d))
+        assert {"boxes.npy", "scores.npy", "count.npy", "empty.npy", "pooled_sample.npy", "rpn_cls.npy"} <= set(files), files
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 << 20
+        import numpy as np
+        arrs = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        assert arrs["boxes.npy"].shape == (8, 100, 7) and arrs["count.npy"].shape == (8,) and arrs["count.npy"].max() > 0
+        dumps.append(arrs)
+    for f, a in dumps[0].items():
+        np.testing.assert_array_equal(dumps[1][f], a, err_msg=f)
+    # ... and they are the LAST timed step's results: priming (one replay per slot) and --settle (whole rounds over the slots) leave
+    # the timed region starting on slot 0, so its 2nd step ran slot 1's own batch.  One process computes slot 1's batch and slot 0's
+    # eagerly (same seeds, same weights): the dump is slot 1's, not slot 0's
+    import torch
+    os.environ.setdefault("WS3D_TUNE_GEMMS", "0")
+    sys.path.insert(0, ROOT)
+    from bench_c3 import C3
+    wl = C3(8, 0, 1, "hdl64", depth=2)
+    own = {}
+    for slot in (1, 0):
+        wl.pts = wl.slot_pts[slot]
+        wl.step(eager=True)
+        torch.cuda.synchronize()
+        _, boxes, scores, count, _, _, _ = wl.last
+        own[slot] = (boxes.cpu().numpy(), scores.cpu().numpy(), count.cpu().numpy())
+    got = dumps[0]
+    assert np.array_equal(own[1][2], got["count.npy"])
+    np.testing.assert_allclose(own[1][0], got["boxes.npy"], rtol=0, atol=1e-4)
+    np.testing.assert_allclose(own[1][1], got["scores.npy"], rtol=0, atol=1e-4)
+    assert not np.allclose(own[0][0], got["boxes.npy"], rtol=0, atol=1e-2), "the dump holds slot 0's batch, not the last step's"
 
 
 def _two_rank_bench(tmp_path, workload_flags, port, ranks=2):
@@ -136,7 +181,7 @@ def _two_rank_bench(tmp_path, workload_flags, port, ranks=2):
 def test_two_ranks_c3_gather_equals_the_single_process_result(tmp_path):
     import numpy as np
     import torch
-    out = _two_rank_bench(tmp_path, ("--workload", "c3", "--pipeline-depth", "2", "--c2-batch", "64"), 29631)
+    out = _two_rank_bench(tmp_path, ("--full", "--workload", "c3", "--pipeline-depth", "2", "--c2-batch", "64"), 29631)
     assert out["n_gpus"] == 2 and out["config"]["workload"].startswith("c3") and out["scaling"] == "weak"
     assert "all_gather" in out["config"]["exchange"] and out["c2_batch"] == 64
     r0, r1 = (np.load(os.path.join(tmp_path, "proposals_rank%d.npz" % r)) for r in (0, 1))
@@ -195,7 +240,7 @@ def test_eight_ranks_batch_64_gather_equals_the_single_process_result(tmp_path):
 
 
 def test_two_ranks_c2_shards_without_a_collective(tmp_path):
-    out = _two_rank_bench(tmp_path, ("--workload", "c2", "--batch", "64"), 29632)
+    out = _two_rank_bench(tmp_path, ("--full", "--workload", "c2", "--batch", "64"), 29632)
     assert out["n_gpus"] == 2 and out["config"]["workload"].startswith("c2") and out["config"]["batch_per_gpu"] == 64
     assert out["value"] > 0 and (out["roofline"]["frac"] is None or 0 < out["roofline"]["frac"] <= 1)
     with open(os.path.join(ROOT, "gpurun_out", "two_rank_c2.json") if os.path.isdir(os.path.join(ROOT, "gpurun_out")) else os.devnull, "w") as f:

@@ -2,19 +2,23 @@
 
 The reference's roipool3d host file carries a complete CPU implementation
 (lib/utils/roipool3d/src/roipool3d.cpp:82-195).  oracle/build_ref.py compiles it
-from the reference tree into oracle/_ref/ (git-ignored, shipped to the GPU box).
-These tests run wherever that .so exists and are skipped otherwise.
+from the reference tree into oracle/_ref/ (git-ignored); tests/golden/make_golden_roipool3d_ref.py
+ran that module once on the inputs below and recorded what it computed in
+tests/golden/roipool3d_ref.npz: the in-box flags (bit-packed), the empty flags, and
+SHA-256 digests of the pooled points / features (the oracle must match them bit for bit).
+The tests read only the recording, so they run wherever the repository is.
 """
+import hashlib
+import os
+
 import numpy as np
 import pytest
 
-torch = pytest.importorskip("torch")
+from ws3d_amd import synth
 
-from oracle import build_ref  # noqa: E402
-from ws3d_amd import synth  # noqa: E402
-
-ref = build_ref.load()
-pytestmark = pytest.mark.skipif(ref is None, reason="oracle/_ref/roipool3d_ref.so not built")
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "roipool3d_ref.npz")
+PIB_CASES = [(2048, 24, 5), (16384, 100, 3000), (4096, 64, 77)]
+POOL_CASES = [(2048, 24, 8, 64, 11), (16384, 100, 128, 512, 3001), (4096, 40, 16, 512, 9), (512, 8, 3, 16, 2)]
 
 
 def _scene(n, m, c, seed, enlarge=1.0):
@@ -29,48 +33,72 @@ def _scene(n, m, c, seed, enlarge=1.0):
     return pc[:, :3].copy(), boxes, feat
 
 
-@pytest.mark.parametrize("n,m,seed", [(2048, 24, 5), (16384, 100, 3000), (4096, 64, 77)])
-def test_pts_in_boxes3d_matches_reference(oracle, n, m, seed):
-    pts, boxes, _ = _scene(n, m, 4, seed)
-    flag_ref = torch.zeros((m, n), dtype=torch.int64)
-    ref.pts_in_boxes3d_cpu(flag_ref, torch.from_numpy(pts), torch.from_numpy(boxes))
-    flag = oracle.pts_in_boxes3d(pts, boxes)
-    assert flag_ref.sum() > 0
-    np.testing.assert_array_equal(flag, flag_ref.numpy())
-
-
-@pytest.mark.parametrize("n,m,c,s,seed", [(2048, 24, 8, 64, 11), (16384, 100, 128, 512, 3001),
-                                          (4096, 40, 16, 512, 9), (512, 8, 3, 16, 2)])
-def test_roipool3d_cpu_matches_reference(oracle, n, m, c, s, seed):
-    pts, boxes, feat = _scene(n, m, c, seed)
-    pp = torch.zeros((m, s, 3))
-    pf = torch.zeros((m, s, c))
-    pe = torch.zeros((m,), dtype=torch.int64)
-    ref.roipool3d_cpu(torch.from_numpy(pts), torch.from_numpy(boxes), torch.from_numpy(feat), pp, pf, pe)
-    o_pts, o_feat, o_empty = oracle.roipool3d_cpu(pts, boxes, feat, s)
-    np.testing.assert_array_equal(o_empty, pe.numpy())
-    np.testing.assert_array_equal(o_pts, pp.numpy())
-    np.testing.assert_array_equal(o_feat, pf.numpy())
-    assert (o_empty == 0).any() and (o_empty == 1).any() or m < 16
-    # the batched GPU-semantics entry point must agree with the CPU twin
-    pooled, empty = oracle.roipool3d(pts[None], boxes[None], feat[None], s)
-    np.testing.assert_array_equal(empty[0], pe.numpy().astype(np.int32))
-    np.testing.assert_array_equal(pooled[0, :, :, :3], pp.numpy())
-    np.testing.assert_array_equal(pooled[0, :, :, 3:], pf.numpy())
-
-
-def test_boundary_and_degenerate_boxes(oracle):
+def _boundary_inputs():
     """points exactly on faces (closed interval), zero-size box, far prefilter (|dx|>10)."""
     box = np.array([[0, 1, 10, 2, 2, 4, 0.0]], dtype=np.float32)  # y in [-1,1], x in [-2,2], z in [9,11]
     pts = np.array([[2, 0, 10], [-2, 0, 10], [0, 1, 11], [0, -1, 9], [2.0000002, 0, 10],
                     [0, 1.0000001, 10], [0, 0, 10], [10.5, 0, 10]], dtype=np.float32)
-    flag_ref = torch.zeros((1, len(pts)), dtype=torch.int64)
-    ref.pts_in_boxes3d_cpu(flag_ref, torch.from_numpy(pts), torch.from_numpy(box))
-    np.testing.assert_array_equal(oracle.pts_in_boxes3d(pts, box), flag_ref.numpy())
-    assert flag_ref.numpy()[0, :4].all() and flag_ref.numpy()[0, 6] == 1
     big = np.array([[0, 1, 10, 2, 30, 30, 0.3]], dtype=np.float32)  # box wider than the 10 m prefilter
     rng = np.random.default_rng(0)
     p2 = rng.uniform([-16, -1, -6], [16, 1, 26], (4000, 3)).astype(np.float32)
-    flag_ref = torch.zeros((1, len(p2)), dtype=torch.int64)
-    ref.pts_in_boxes3d_cpu(flag_ref, torch.from_numpy(p2), torch.from_numpy(big))
-    np.testing.assert_array_equal(oracle.pts_in_boxes3d(p2, big), flag_ref.numpy())
+    return (pts, box), (p2, big)
+
+
+def digest(*arrays):
+    """SHA-256 over the float32 bytes of the arrays (C order): equal digests = bit-identical arrays"""
+    h = hashlib.sha256()
+    for a in arrays:
+        h.update(np.ascontiguousarray(a, dtype=np.float32).tobytes())
+    return h.hexdigest()
+
+
+def _key(*case):
+    return "_".join(str(v) for v in case)
+
+
+@pytest.fixture(scope="module")
+def rec():
+    with np.load(GOLDEN) as z:
+        return {k: z[k] for k in z.files}
+
+
+def _flags(rec, key, shape):
+    return np.unpackbits(rec[key], axis=1, count=shape[1]).astype(np.int64)
+
+
+@pytest.mark.parametrize("n,m,seed", PIB_CASES)
+def test_pts_in_boxes3d_matches_reference(oracle, rec, n, m, seed):
+    pts, boxes, _ = _scene(n, m, 4, seed)
+    k = _key("pib", n, m, seed)
+    assert str(rec[k + "_inputs"]) == digest(pts, boxes), "the scene generator changed: re-record the fixture"
+    flag_ref = _flags(rec, k + "_flag", (m, n))
+    flag = oracle.pts_in_boxes3d(pts, boxes)
+    assert flag_ref.sum() > 0
+    np.testing.assert_array_equal(flag, flag_ref)
+
+
+@pytest.mark.parametrize("n,m,c,s,seed", POOL_CASES)
+def test_roipool3d_cpu_matches_reference(oracle, rec, n, m, c, s, seed):
+    pts, boxes, feat = _scene(n, m, c, seed)
+    k = _key("pool", n, m, c, s, seed)
+    assert str(rec[k + "_inputs"]) == digest(pts, boxes, feat), "the scene generator changed: re-record the fixture"
+    pe = rec[k + "_empty"]
+    o_pts, o_feat, o_empty = oracle.roipool3d_cpu(pts, boxes, feat, s)
+    np.testing.assert_array_equal(o_empty, pe)
+    assert o_pts.shape == (m, s, 3) and o_feat.shape == (m, s, c)
+    assert digest(o_pts) == str(rec[k + "_pooled_pts"]), "pooled points differ from the reference's"
+    assert digest(o_feat) == str(rec[k + "_pooled_feat"]), "pooled features differ from the reference's"
+    assert (o_empty == 0).any() and (o_empty == 1).any() or m < 16
+    # the batched GPU-semantics entry point must agree with the CPU twin
+    pooled, empty = oracle.roipool3d(pts[None], boxes[None], feat[None], s)
+    np.testing.assert_array_equal(empty[0], pe.astype(np.int32))
+    np.testing.assert_array_equal(pooled[0, :, :, :3], o_pts)
+    np.testing.assert_array_equal(pooled[0, :, :, 3:], o_feat)
+
+
+def test_boundary_and_degenerate_boxes(oracle, rec):
+    (pts, box), (p2, big) = _boundary_inputs()
+    flag_ref = _flags(rec, "boundary_flag", (1, len(pts)))
+    np.testing.assert_array_equal(oracle.pts_in_boxes3d(pts, box), flag_ref)
+    assert flag_ref[0, :4].all() and flag_ref[0, 6] == 1
+    np.testing.assert_array_equal(oracle.pts_in_boxes3d(p2, big), _flags(rec, "prefilter_flag", (1, len(p2))))
