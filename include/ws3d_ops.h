@@ -624,6 +624,44 @@ WS3D_API int ws3d_roipool3d_ws(int batch_size, int pts_num, int boxes_num, int f
 WS3D_API int ws3d_pts_in_boxes3d(int boxes_num, int pts_num, const float *pts, const float *boxes3d,
                         int64_t *flag, ws3d_stream_t stream);
 
+/* ------------------------------------------------- KITTI evaluation (kitti_object_eval_python) */
+
+/* Frames are CSR ranges: gt_off / dt_off (frames + 1) int32 offsets of each frame's ground truths / detections, out_off (frames + 1)
+ * int64 offset of each frame's (n_dt x n_gt) overlap block (row = detection, as eval_class's calculate_iou_partly(dt_annos, gt_annos),
+ * eval.py:468).  All data float64 unless stated.  Additive to ABI 6: no existing entry changed.                                       */
+
+/* Per-frame overlap blocks, every frame in one launch: replaces calculate_iou_partly (eval.py:335-410), whose cross-frame matrix per
+ * group of frames is only read on its diagonal blocks.  out[out_off[f] + j * n_gt + i] = overlap(detection j, ground truth i):
+ *   metric 0  boxes (n, 4) image boxes: image_box_overlap (eval.py:84-111) in double, criterion -1 / 0 / 1 / 2;
+ *   metric 1  boxes (n, 5) (x, z, l, w, ry) rounded to fp32: rotate_iou_gpu_eval / devRotateIoUEval (rotate_iou.py:16-329) in fp32,
+ *             the ground truth as the query box rbox1, criterion -1 / 0 / 1 / 2;
+ *   metric 2  boxes (n, 7) (x, y, z, l, h, w, ry): d3_box_overlap (eval.py:119-152), the fp32 BEV intersection of columns
+ *             [0, 2, 3, 5, 6] and the height / volume part in double, stored rounded to fp32.
+ * max_pairs >= max over frames of n_dt * n_gt (any value >= it; 0 = nothing to do).  Any box count per frame, 0 included.           */
+WS3D_API int ws3d_kitti_overlaps(int metric, int criterion, int frames, long max_pairs, const int32_t *gt_off, const int32_t *dt_off,
+                                 const int64_t *out_off, const double *dt_boxes, const double *gt_boxes, double *out,
+                                 ws3d_stream_t stream);
+
+/* The collection pass of eval_class (eval.py:480-494): compute_statistics_jit (eval.py:155-273) with thresh = 0, compute_fp = False
+ * for every frame.  ignored_gt / ignored_dt int32 per box (clean_data, eval.py:28-81), dt_score per detection; out per ground truth:
+ * tp_flag int32 = 1 where it was matched as a true positive, tp_score = that detection's score (0 elsewhere).  The reference's
+ * thresholds list is tp_score[tp_flag == 1] in (frame, ground truth) order.  max_dt >= the largest n_dt (at most 4096).             */
+WS3D_API int ws3d_kitti_collect_scores(int frames, int max_dt, const int32_t *gt_off, const int32_t *dt_off, const int64_t *out_off,
+                                       const double *overlaps, const int32_t *ignored_gt, const int32_t *ignored_dt,
+                                       const double *dt_score, double min_overlap, double *tp_score, int32_t *tp_flag,
+                                       ws3d_stream_t stream);
+
+/* The counting pass: fused_compute_statistics (eval.py:285-333) over num_thresh score thresholds for every frame, compute_fp = True,
+ * with the DontCare suppression of metric 0 (dc_off (frames + 1) int32, dc_bbox (n_dc, 4)) and, if compute_aos, the orientation
+ * similarity (dt_alpha / gt_alpha).  pr (num_thresh, 4) = tp, fp, fn, similarity summed over the frames in frame order (exact
+ * counts, reproducible sums: no atomics).  workspace >= ws3d_kitti_count_workspace_bytes(frames, num_thresh) bytes of device memory. */
+WS3D_API size_t ws3d_kitti_count_workspace_bytes(int frames, int num_thresh);
+WS3D_API int ws3d_kitti_count(int metric, int frames, int max_dt, int num_thresh, const double *thresholds, const int32_t *gt_off,
+                              const int32_t *dt_off, const int32_t *dc_off, const int64_t *out_off, const double *overlaps,
+                              const int32_t *ignored_gt, const int32_t *ignored_dt, const double *dt_score, const double *dt_alpha,
+                              const double *gt_alpha, const double *dt_bbox, const double *dc_bbox, double min_overlap, int compute_aos,
+                              void *workspace, size_t workspace_bytes, double *pr, ws3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

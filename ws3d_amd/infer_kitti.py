@@ -66,10 +66,19 @@ def main():
     ap.add_argument("--npoints", type=int, default=16384)
     ap.add_argument("--pipeline_depth", type=int, default=4, help="batches in flight on separate HIP streams")
     ap.add_argument("--workers", type=int, default=0, help="loader processes reading / sampling the next scans")
+    ap.add_argument("--eval", action="store_true",
+                    help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
     a = ap.parse_args()
     ensure_hw_queues()
     files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.npoints, depth=a.pipeline_depth, workers=a.workers)
     print(f"{len(files)} result files in {a.out}")
+    if a.eval:
+        from . import kitti_eval
+        result, ret = kitti_eval.evaluate(os.path.join(a.root, "training", "label_2"), a.out,
+                                          os.path.join(a.root, "ImageSets", a.split + ".txt"), current_class=0)
+        print(result, end="")
+        for k, v in ret.items():
+            print(f"{k}: {v:.4f}")
 
 
 if __name__ == "__main__":

@@ -12,6 +12,7 @@ Reference behaviour reproduced (file:line in /root/reference):
     project, filter, near/far sampling with the *global* ``numpy.random`` stream, intensity - 0.5
   * ``save_kitti_format`` (tools/eval_auto.py:108-135)
   * ``Object3d`` label parsing (lib/utils/object3d.py:12-33)
+  * the evaluator's annotation dicts ``get_label_anno(s)`` (tools/kitti_object_eval_python/kitti_common.py:293-347)
 
 The sampler draws from ``numpy.random`` in exactly the reference's call order, so with the same
 seed it selects the same points as the reference data loader (tests/golden/kitti_ingest.json).
@@ -19,6 +20,7 @@ seed it selects the same points as the reference data loader (tests/golden/kitti
 from __future__ import annotations
 
 import os
+import re
 import struct
 from dataclasses import dataclass
 from typing import Sequence, Tuple
@@ -148,6 +150,39 @@ class Object3d:
 def read_label_file(path: str):
     with open(path) as f:
         return [Object3d.from_line(line) for line in f.readlines() if line.strip()]
+
+
+def read_label_anno(path: str) -> dict:
+    """one label / result file as the evaluator's annotation dict (kitti_common.get_label_anno,
+    tools/kitti_object_eval_python/kitti_common.py:293-331): dimensions reordered from the file's h, w, l
+    to l, h, w; ``score`` from a 16th field, zeros without one; an empty file gives empty arrays"""
+    with open(path) as f:
+        rows = [line.strip().split(" ") for line in f.readlines()]
+    anno = {
+        "name": np.array([r[0] for r in rows]),
+        "truncated": np.array([float(r[1]) for r in rows]),
+        "occluded": np.array([int(r[2]) for r in rows]),
+        "alpha": np.array([float(r[3]) for r in rows]),
+        "bbox": np.array([[float(v) for v in r[4:8]] for r in rows]).reshape(-1, 4),
+        "dimensions": np.array([[float(v) for v in r[8:11]] for r in rows]).reshape(-1, 3)[:, [2, 0, 1]],
+        "location": np.array([[float(v) for v in r[11:14]] for r in rows]).reshape(-1, 3),
+        "rotation_y": np.array([float(r[14]) for r in rows]).reshape(-1),
+    }
+    if rows and len(rows[0]) == 16:
+        anno["score"] = np.array([float(r[15]) for r in rows])
+    else:
+        anno["score"] = np.zeros([len(anno["bbox"])])
+    return anno
+
+
+def read_label_annos(folder: str, image_ids=None) -> list:
+    """the annotation dicts of ``folder/%06d.txt`` (kitti_common.get_label_annos, kitti_common.py:333-347): every
+    six-digit file in ascending id order when ``image_ids`` is None, ids 0..n-1 for an int n, else the ids given"""
+    if image_ids is None:
+        image_ids = sorted(int(f[:6]) for f in os.listdir(folder) if re.match(r"^\d{6}.txt$", f))
+    if not isinstance(image_ids, list):
+        image_ids = list(range(image_ids))
+    return [read_label_anno(os.path.join(folder, "%06d.txt" % idx)) for idx in image_ids]
 
 
 # ----------------------------------------------------------------------------- filter + sampler
