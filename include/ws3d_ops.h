@@ -467,6 +467,20 @@ WS3D_API int ws3d_sa_mlp3_pool(long rows, int nsample, int c1, int c2, int c3, c
 WS3D_API int ws3d_mlp2_rows(long rows, int k_dim, int o1, int o2, const float *x_rows, const float *w1t, const float *b1, int relu1,
                    const float *w2t, const float *b2, int relu2, float *out, int *ticket, ws3d_stream_t stream);
 
+/* The RPN's two heads in ONE launch on the bf16 matrix cores at fp32 accuracy (split product: DESIGN.md section 4):
+ *   out_cls (rows, 1)  = relu2?(relu1?(x @ W1c + b1c) @ W2c + b2c),   out_reg (rows, o2) likewise with the regression head's weights,
+ * x (rows, 128) row-major, rows % 32 == 0.  Each head's weights are packed once per weight set by ws3d_rpn_heads_pack into a device
+ * blob of ws3d_rpn_heads_blob_bytes(o2) bytes (16-byte aligned; 0 = o2 not covered: 1 .. 64; the regression head takes o2 >= 2); w1t (128, 128)
+ * and w2t (128, o2) as ws3d_mlp2_rows takes them, biases may be NULL.  heads: 1 = the classification head only (blob_cls, o2 = 1),
+ * 2 = the regression head only, 3 = both in one launch.  ticket_cls / ticket_reg: one device int each, ZERO on entry (consumed).
+ * workgroups: of the whole launch, 0 = one per CU.  Deterministic: the outputs do not depend on the order the tickets hand out the
+ * tiles.  Other shapes return WS3D_E_UNSUPPORTED (the caller runs ws3d_mlp2_rows).  ws3d extension, used by ws3d_amd/fastpath.py. */
+WS3D_API size_t ws3d_rpn_heads_blob_bytes(int o2);
+WS3D_API int ws3d_rpn_heads_pack(int o2, const float *w1t, const float *b1, int relu1, const float *w2t, const float *b2, int relu2, void *blob,
+                        ws3d_stream_t stream);
+WS3D_API int ws3d_rpn_heads(long rows, const float *x_rows, int heads, const void *blob_cls, float *out_cls, int *ticket_cls, int o2_reg,
+                   const void *blob_reg, float *out_reg, int *ticket_reg, int workgroups, ws3d_stream_t stream);
+
 /* Both layers of a two-layer feature-propagation module in one kernel (round 4): the first layer's rows are built in the A operand of the
  * second layer's product exactly as ws3d_qinterp_rows builds them,
  *   x = relu1?( w0 Q[i0] + w1 Q[i1] + w2 Q[i2] + (lin (b*n, c)  |  skip (b*n, c1 <= 4) @ wb (c1, c) + b1) ),   out (b*n, o) = relu2?( x @ w2t (c, o) + b2 )

@@ -76,6 +76,9 @@ SIGNATURES = {
     "ws3d_sa_mlp3_pool": (_i, [C.c_long, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "ws3d_qinterp_gemm": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "ws3d_mlp2_rows": (_i, [C.c_long, _i, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ws3d_rpn_heads_blob_bytes": (_sz, [_i]),
+    "ws3d_rpn_heads_pack": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
+    "ws3d_rpn_heads": (_i, [C.c_long, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
     "ws3d_decode_center_boxes": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ws3d_topk_sorted": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "ws3d_topk_workspace_bytes": (C.c_size_t, [_i, _i]),

@@ -896,6 +896,52 @@ def mlp2_rows(x2d, w1t, b1, relu1, w2t, b2, relu2, ticket=None):
     return out
 
 
+def rpn_heads_pack(w1t, b1, relu1, w2t, b2, relu2):
+    """one head's weights (w1t (128,128), w2t (128,O2) as mlp2_rows takes them) split into bf16 pieces and packed for rpn_heads
+    (ws3d_rpn_heads_pack: one small launch) -> a device blob, or None when O2 is not covered (1 .. 64).
+    The caller caches it per weight set.  ws3d extension."""
+    dev = _dev(w1t, w2t)
+    _f32(w1t, "w1t"); _f32(w2t, "w2t")
+    O2 = w2t.size(1) if w2t.dim() == 2 else 0
+    n = int(_lib.load().ws3d_rpn_heads_blob_bytes(O2))
+    if n == 0 or tuple(w1t.shape) != (128, 128) or w2t.size(0) != 128 or not w1t.is_contiguous() or not w2t.is_contiguous():
+        return None
+    for b, nm, o in ((b1, "b1", 128), (b2, "b2", O2)):
+        if b is not None:
+            _f32(b, nm)
+            if b.numel() != o or not b.is_contiguous():
+                return None
+    blob = torch.empty((n + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    with _on(dev):
+        check(_lib.load().ws3d_rpn_heads_pack(O2, _p(w1t), _p(b1), int(bool(relu1)), _p(w2t), _p(b2), int(bool(relu2)), _p(blob), _stream()),
+              "rpn_heads_pack")
+    return blob
+
+
+def rpn_heads(x2d, heads, blob_cls, blob_reg, o2_reg, tickets, workgroups=0):
+    """the RPN's two heads over rows x2d (R,128) on the bf16 matrix cores at fp32 accuracy (ws3d_rpn_heads): heads 1 = the
+    classification head (blob_cls, one output), 2 = the regression head (blob_reg, o2_reg outputs), 3 = both in one launch.
+    Blobs from rpn_heads_pack; tickets: a ZEROED int32 tensor of 2 elements (cls, reg; consumed); workgroups: of the launch
+    (0 = one per CU).  -> (cls (R,1) or None, reg (R,o2_reg) or None), or None when the shape is not covered (nothing launched:
+    the caller runs mlp2_rows).  ws3d extension."""
+    dev = _dev(x2d)
+    _f32(x2d, "x2d")
+    if (x2d.dim() != 2 or x2d.size(1) != 128 or x2d.size(0) % 32 or not x2d.is_contiguous() or heads not in (1, 2, 3) or
+            tickets is None or tickets.dtype != torch.int32 or tickets.numel() < 2 or not tickets.is_contiguous()):
+        return None
+    R = x2d.size(0)
+    out_cls = torch.empty((R, 1), dtype=torch.float32, device=dev) if heads & 1 else None
+    out_reg = torch.empty((R, int(o2_reg)), dtype=torch.float32, device=dev) if heads & 2 else None
+    with _on(dev):
+        rc = _lib.load().ws3d_rpn_heads(R, _p(x2d), int(heads), _p(blob_cls) if heads & 1 else None, _p(out_cls), _p(tickets[0:1]),
+                                        int(o2_reg) if heads & 2 else 0, _p(blob_reg) if heads & 2 else None, _p(out_reg), _p(tickets[1:2]),
+                                        int(workgroups), _stream())
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    check(rc, "rpn_heads")
+    return out_cls, out_reg
+
+
 def pool_nsample(x):
     """x (..., nsample) contiguous fp32 -> (max over the last axis (...), position of the maximum u8);
     F.max_pool2d(kernel=[1, nsample]) scan rule (first maximum, NaN propagates).  ws3d extension."""

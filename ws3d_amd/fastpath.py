@@ -101,6 +101,7 @@ FUSED_PROLOGUE = True   # the coordinate / feature split of the input rows and t
 MERGED_BINNING = True   # serial order (graph capture): the binned copies of levels 2.. (ball query's grid + three_nn's (x, z) grid) in ONE launch behind the sampling chain (ws3d_sort_points_jobs) instead of one per level and flavour
 PER_POINT_FP = True  # FP modules: first layer as (known_feats @ W_a) interpolated + skip @ W_b (ws3d_qinterp_rows)
 FUSED_MLP2_ROWS = True  # ws3d_mlp2_rows: the two layers of a head in one kernel
+FUSED_HEADS = True  # ws3d_rpn_heads: both heads in ONE launch on the bf16 matrix cores at fp32 accuracy (split product); False: the two ws3d_mlp2_rows launches
 FUSED_GATHER_GEMM2 = True  # ws3d_gather_gemm2: layers 1 + 2 of SA2-SA4 in one kernel
 BIN_INPUT_AHEAD = True     # eager pass with geometry ahead: bin the input cloud on the search stream beside the first level's sampling kernel
 FUSED_QINTERP_GEMM_MIN_ROWS = 30000    # ws3d_qinterp_gemm (both layers of an FP module in one kernel) from this many rows on (batch 8: FP1, FP2; smaller modules lose, profiles/r04_qinterp_gemm_ab.txt); 1 << 60: never
@@ -176,6 +177,39 @@ def mlp_rows(x2d: torch.Tensor, seq, ticket=None) -> torch.Tensor:
     for blk in blocks:
         x2d = _layer(x2d, blk)
     return x2d
+
+
+def _heads_blob(seq):
+    """(packed blob, o2) of a head Sequential for ws3d_rpn_heads, cached on its first block and replaced when the folded weights
+    change (a captured graph that reads it keeps its own reference: Stage1Pipeline's slots), or None when not covered"""
+    blocks = _blocks(seq)
+    if len(blocks) != 2:
+        return None
+    (w1, b1, r1), (w2, b2, r2) = _row_weights(blocks[0]), _row_weights(blocks[1])
+    cache = blocks[0].__dict__.get("_heads_blob")
+    if cache is None or cache[0] is not w1 or cache[1] is not b1 or cache[2] is not w2 or cache[3] is not b2:
+        cache = (w1, b1, w2, b2, _C.rpn_heads_pack(w1, b1, r1, w2, b2, r2), w2.size(1))
+        if not torch.cuda.is_current_stream_capturing():
+            blocks[0].__dict__["_heads_blob"] = cache
+    return None if cache[4] is None else (cache[4], cache[5])
+
+
+def heads_blobs(rpn):
+    """the packed head blobs rpn_forward launches with (for a holder of a captured graph that reads them)"""
+    return [blk.__dict__["_heads_blob"][4] for seq in (rpn.rpn_cls_layer, rpn.rpn_reg_layer) for blk in _blocks(seq)[:1]
+            if "_heads_blob" in blk.__dict__]
+
+
+def _fused_heads(rows: torch.Tensor, blobs, which: int, tickets):
+    """ws3d_rpn_heads over the rows for which = 1 (cls), 2 (reg) or 3 (both in one launch) -> (cls, reg), or None (not covered:
+    nothing launched).  Workgroups: the heads' knob (ws3d_tune key 1, per head: a pipeline that captures many batches in flight
+    narrows it) times the heads in the launch; 0 = one per CU."""
+    if blobs is None or not all(blobs[i] is not None for i in (0, 1) if which & (1 << i)):
+        return None
+    (bc, oc), (br, orr) = blobs[0] or (None, 1), blobs[1] or (None, 0)
+    if oc != 1 or (which & 2 and orr == 1):
+        return None
+    return _C.rpn_heads(rows, which, bc, br, orr, tickets, _C.tune("mlp2_wgs") * (2 if which == 3 else 1))
 
 
 def supported(model) -> bool:
@@ -776,7 +810,9 @@ def rpn_forward(model, pts_input: torch.Tensor, defer_reg_join: bool = False) ->
     xyz, feats = backbone_forward(rpn.backbone_net, pts_input, zeros)     # (B,N,3), (B,N,128)
     B, N, C = feats.shape
     rows = feats.view(B * N, C)
-    tickets = zeros.take((2,), torch.int32) if FUSED_MLP2_ROWS else (None, None)
+    tickets = zeros.take((2,), torch.int32) if (FUSED_MLP2_ROWS or FUSED_HEADS) else (None, None)
+    # packed on the caller's stream before any fork (the blobs are cached: one pack per weight set)
+    blobs = (_heads_blob(rpn.rpn_cls_layer), _heads_blob(rpn.rpn_reg_layer)) if FUSED_HEADS else None
     reg_ready = None
     if PARALLEL_HEADS and _geometry_ahead_now() and not torch.cuda.is_current_stream_capturing():
         main = torch.cuda.current_stream(rows.device)
@@ -785,20 +821,26 @@ def rpn_forward(model, pts_input: torch.Tensor, defer_reg_join: bool = False) ->
         fork.record(main)
         aux.wait_event(fork)
         with torch.cuda.stream(aux):
-            rpn_reg = mlp_rows(rows, rpn.rpn_reg_layer, tickets[1:2]).view(B, N, -1)
+            fused = _fused_heads(rows, blobs, 2, tickets)
+            rpn_reg = (fused[1] if fused is not None else mlp_rows(rows, rpn.rpn_reg_layer, tickets[1:2])).view(B, N, -1)
             reg_ready = torch.cuda.Event()
             reg_ready.record(aux)
         # rpn_reg's block belongs to the aux stream's pool but is read on the caller's stream (and whichever stream consumes the
         # dict): without this the caching allocator may hand the block to another pass's aux-stream allocation as soon as the
         # tensor is dropped, while a kernel of the caller's stream still reads it (several caller streams share the pooled aux)
         rpn_reg.record_stream(main)
-        rpn_cls = mlp_rows(rows, rpn.rpn_cls_layer, tickets[0:1]).view(B, N, -1)
+        fused = _fused_heads(rows, blobs, 1, tickets)
+        rpn_cls = (fused[0] if fused is not None else mlp_rows(rows, rpn.rpn_cls_layer, tickets[0:1])).view(B, N, -1)
         if not defer_reg_join:
             main.wait_event(reg_ready)
             reg_ready = None
     else:
-        rpn_cls = mlp_rows(rows, rpn.rpn_cls_layer, tickets[0:1]).view(B, N, -1)
-        rpn_reg = mlp_rows(rows, rpn.rpn_reg_layer, tickets[1:2]).view(B, N, -1)
+        fused = _fused_heads(rows, blobs, 3, tickets)
+        if fused is not None:
+            rpn_cls, rpn_reg = fused[0].view(B, N, -1), fused[1].view(B, N, -1)
+        else:
+            rpn_cls = mlp_rows(rows, rpn.rpn_cls_layer, tickets[0:1]).view(B, N, -1)
+            rpn_reg = mlp_rows(rows, rpn.rpn_reg_layer, tickets[1:2]).view(B, N, -1)
     global LAST_ARENA_FALLBACKS
     LAST_ARENA_FALLBACKS = zeros.fallbacks if not zeros.fallbacks else getattr(zeros, "fallback_shapes", zeros.fallbacks)
     out = {"rpn_cls": rpn_cls, "rpn_reg": rpn_reg, "backbone_xyz": xyz,

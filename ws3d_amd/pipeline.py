@@ -205,6 +205,7 @@ class Stage1Pipeline:
             with fastpath.compact_only_scales(self.compact_only), torch.cuda.graph(graph, stream=stream):
                 slot["out"] = self.body(slot["inp"], slot["exchange"])
             slot["graph"] = graph
+            slot["heads_blobs"] = fastpath.heads_blobs(self.model.rpn)       # the packed head weights the graph reads (the blocks' caches may be replaced)
         except Exception as exc:      # capture is an optimisation: fall back to eager launches on the slot streams
             self.graph_error = repr(exc)
             slot["graph"] = None
