@@ -17,6 +17,7 @@ from __future__ import annotations
 
 import argparse
 import concurrent.futures as cf
+import glob
 import os
 import shutil
 import subprocess
@@ -45,7 +46,8 @@ def hipcc() -> str:
 
 
 def _deps(src: str):
-    return [src, os.path.join(CSRC, "common.h"), os.path.join(CSRC, "binning.h"), os.path.join(CSRC, "compact_pool.h"), os.path.join(HERE, "..", "include", "ws3d_ops.h"),
+    # every header of csrc/ is a dependency of every translation unit
+    return [src, *glob.glob(os.path.join(CSRC, "*.h")), os.path.join(HERE, "..", "include", "ws3d_ops.h"),
             os.path.join(CSRC, "exports.map"), os.path.abspath(__file__)]
 
 

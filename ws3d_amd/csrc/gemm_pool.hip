@@ -6,115 +6,19 @@
 // accumulated on the matrix cores (v_mfma_f32_32x32x2_f32: fp32 in, fp32 accumulate -- same precision
 // class as the library GEMM, different summation order) and reduced over its row groups in registers;
 // only the pooled rows reach HBM.
+// Every kernel of this file is put together from the blocks of mfma_tile.h: an A-operand loader, the K loop and / or the layer
+// out of an LDS activation tile, and an epilogue.
 #include <cstdlib>
 
 #include "common.h"
 #include "compact_pool.h"
+#include "mfma_tile.h"
 
 namespace ws3d {
 
-typedef float floatx16 __attribute__((ext_vector_type(16)));
-
-constexpr int GP_KT = 16;          // K step per LDS tile
-constexpr int GP_XS = 65;          // padded row length of the k-major X tile
-
-__device__ __forceinline__ float gp_nanmax(float a, float b) { return (a > b || a != a) ? a : b; }
-
-// grid (O / 64, R / 64), 256 threads = 4 waves as 2 (rows) x 2 (cols) sub-tiles of 32 x 32
-template <int NS>
-__global__ __launch_bounds__(256) void gemm_pool_kernel(int k_dim, int o_dim, const float *__restrict__ x,
-                                                        const float *__restrict__ wt, const float *__restrict__ bias,
-                                                        int relu, float *__restrict__ out, int out_stride, int xcd,
-                                                        const int32_t *__restrict__ gate, long gate_limit) {
-    if (gate && (long)*gate <= gate_limit) return;        // device-side dispatch (ws3d_ops.h "launch gates"): the compact kernels run instead
-    __shared__ float xs[2][GP_KT][GP_XS];     // [k][row]
-    __shared__ float ws[2][GP_KT][64];        // [k][col]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    // 1-D grid; the col tiles of a row tile read the SAME activation rows: next to each other on ONE XCD (workgroup g runs on
-    // XCD g % 8) the second .. eighth read hits that L2 (with col tiles on blockIdx.x they ran on different XCDs and the
-    // activation -- 100 MB at SA2 -- came out of HBM once per col tile)
-    const int col_tiles = o_dim / 64;
-    long row_tile;
-    int col_tile;
-    {
-        const long g = blockIdx.x;
-        if (xcd) {
-            const long j = g >> 3;
-            col_tile = (int)(j % col_tiles);
-            row_tile = (j / col_tiles) * 8 + (g & 7);
-        } else {
-            col_tile = (int)(g % col_tiles);
-            row_tile = g / col_tiles;
-        }
-    }
-    const long row0 = row_tile * 64;
-    const int col0 = col_tile * 64;
-    // global -> register staging: X tile 64 rows x 16 k (one float4 per thread), W tile 16 k x 64 cols
-    const int xr = tid >> 2, xk = (tid & 3) * 4;
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const float *xp = x + (row0 + xr) * (long)k_dim;
-    auto load_x = [&](int k0) {
-        const int k = k0 + xk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(xp + k) : make_float4(0.f, 0.f, 0.f, 0.f);   // k_dim % 4 == 0
-    };
-    auto load_w = [&](int k0) {
-        const int k = k0 + wk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)k * o_dim + col0 + wc) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int buf, const float4 xv, const float4 wv) {
-        xs[buf][xk + 0][xr] = xv.x; xs[buf][xk + 1][xr] = xv.y; xs[buf][xk + 2][xr] = xv.z; xs[buf][xk + 3][xr] = xv.w;
-        *reinterpret_cast<float4 *>(&ws[buf][wk][wc]) = wv;
-    };
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 xv = load_x(0), wv = load_w(0);
-    stage(0, xv, wv);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) { xv = load_x((t + 1) * GP_KT); wv = load_w((t + 1) * GP_KT); }
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[cur][k + kh][ar], ws[cur][k + kh][bc], acc, 0, 0, 0);
-        if (t + 1 < ntiles) stage(cur ^ 1, xv, wv);
-        __syncthreads();
-    }
-    // accumulator layout (32 x 32 tile): register v of lane l holds row 8*(v/4) + 4*(l/32) + v%4, column l%32
-    const int col = col0 + bc;
-    const float bv = bias ? bias[col] : 0.f;
-    if (NS == 16) {
-        float m0 = acc[0], m1 = acc[8];
-#pragma unroll
-        for (int v = 1; v < 8; ++v) { m0 = gp_nanmax(m0, acc[v]); m1 = gp_nanmax(m1, acc[8 + v]); }
-        m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-        m1 = gp_nanmax(m1, __shfl_xor(m1, 32));
-        if (lane < 32) {
-            const long g = (row0 + wm * 32) / 16;
-            float r0 = m0 + bv, r1 = m1 + bv;
-            if (relu) { r0 = r0 < 0.f ? 0.f : r0; r1 = r1 < 0.f ? 0.f : r1; }
-            out[g * out_stride + col] = r0;
-            out[(g + 1) * out_stride + col] = r1;
-        }
-    } else {   // NS == 32: the whole sub-tile is one group
-        float m0 = acc[0];
-#pragma unroll
-        for (int v = 1; v < 16; ++v) m0 = gp_nanmax(m0, acc[v]);
-        m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-        if (lane < 32) {
-            const long g = (row0 + wm * 32) / 32;
-            float r0 = m0 + bv;
-            if (relu) r0 = r0 < 0.f ? 0.f : r0;
-            out[g * out_stride + col] = r0;
-        }
-    }
-}
-
-// The same product with a (64 MB) x (64 NB) output tile per workgroup: each of the 2 x 2 waves holds MB x NB accumulators of
-// 32 x 32, one k-step costs MB + NB LDS reads for MB NB matrix instructions, and the L2 -> LDS traffic per flop falls with the
+// 1-D grid of (O / 64 NB) * (R / 64 MB) workgroups in gg_tile's order, 256 threads; (MB, NB) = (1, 1) is the 64 x 64 tile.  With
+// a (64 MB) x (64 NB) output tile per workgroup each of the 2 x 2 waves holds MB x NB accumulators of 32 x 32, one k-step costs
+// MB + NB LDS reads for MB NB matrix instructions, and the L2 -> LDS traffic per flop falls with the
 // tile (64 x 64: 16 flop per byte, 128 x 128: 32).  Measured on the six last-layer shapes (scripts/ubench/gemm_pool_tiles.sh,
 // profiles/r02_gemm_pool_tiles.txt): L2 requests and LDS cycles halve at 128 x 128, the kernel time does not move (0.288 vs
 // 0.293 ms in total): SQ_VALU_MFMA_BUSY_CYCLES = 64 clk x the instruction count at every tile, i.e. the matrix pipe is busy
@@ -125,135 +29,27 @@ __global__ __launch_bounds__(256) void gemm_pool_big_kernel(int k_dim, int o_dim
                                                             const float *__restrict__ wt, const float *__restrict__ bias,
                                                             int relu, float *__restrict__ out, int out_stride, int xcd,
                                                             const int32_t *__restrict__ gate, long gate_limit) {
-    if (gate && (long)*gate <= gate_limit) return;
-    constexpr int TM = 64 * MB, TN = 64 * NB, XS = TM + 1;
-    __shared__ float xs[2][GP_KT][XS];        // [k][row]
-    __shared__ float ws[2][GP_KT][TN];        // [k][col]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    const int col_tiles = o_dim / TN;
+    if (gate && (long)*gate <= gate_limit) return;        // device-side dispatch (ws3d_ops.h "launch gates"): the compact kernels run instead
+    constexpr int TM = 64 * MB, TN = 64 * NB;
+    __shared__ float xs[2][GP_KT][TM + 1];                                      // [k][row]
+    __shared__ __attribute__((aligned(16))) float ws[2][GP_KT][TN];             // [k][col]
+    const Wave w;
     long row_tile;
     int col_tile;
-    {
-        const long g = blockIdx.x;
-        if (xcd) {
-            const long j = g >> 3;
-            col_tile = (int)(j % col_tiles);
-            row_tile = (j / col_tiles) * 8 + (g & 7);
-        } else {
-            col_tile = (int)(g % col_tiles);
-            row_tile = g / col_tiles;
-        }
-    }
+    gg_tile<false>(o_dim / TN, xcd, blockIdx.x, row_tile, col_tile);
     const long row0 = row_tile * TM;
     const int col0 = col_tile * TN;
-    float4 xv[MB], wv[NB];
-    auto load = [&](int k0) {
+    RowsA<MB> load_a;
+    load_a.k_dim = k_dim;
 #pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            const int idx = tid + 256 * i, r = idx >> 2, k = k0 + (idx & 3) * 4;
-            xv[i] = k < k_dim ? *reinterpret_cast<const float4 *>(x + (row0 + r) * (long)k_dim + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int idx = tid + 256 * j, k = k0 + idx / (16 * NB), c = (idx % (16 * NB)) * 4;
-            wv[j] = k < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)k * o_dim + col0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            const int idx = tid + 256 * i, r = idx >> 2, k = (idx & 3) * 4;
-            xs[buf][k + 0][r] = xv[i].x; xs[buf][k + 1][r] = xv[i].y; xs[buf][k + 2][r] = xv[i].z; xs[buf][k + 3][r] = xv[i].w;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int idx = tid + 256 * j;
-            *reinterpret_cast<float4 *>(&ws[buf][idx / (16 * NB)][(idx % (16 * NB)) * 4]) = wv[j];
-        }
-    };
+    for (int i = 0; i < MB; ++i) load_a.p[i] = x + (row0 + (w.tid >> 2) + 64 * i) * (long)k_dim;
     floatx16 acc[MB][NB];
+    mfma_k_loop<MB, NB, false>(w, acc, xs, ws, k_dim, load_a, wt, o_dim, col0);
 #pragma unroll
     for (int i = 0; i < MB; ++i)
 #pragma unroll
         for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-    load(0);
-    stage(0);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 * MB + (lane & 31), bc = wn * 32 * NB + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) load((t + 1) * GP_KT);
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2) {
-            float a[MB], bq[NB];
-#pragma unroll
-            for (int i = 0; i < MB; ++i) a[i] = xs[cur][k + kh][ar + 32 * i];
-#pragma unroll
-            for (int j = 0; j < NB; ++j) bq[j] = ws[cur][k + kh][bc + 32 * j];
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bq[j], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < ntiles) stage(cur ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int col = col0 + bc + 32 * j;
-            const float bv = bias ? bias[col] : 0.f;
-            const long rbase = row0 + wm * 32 * MB + 32 * i;
-            if (NS == 16) {
-                float m0 = acc[i][j][0], m1 = acc[i][j][8];
-#pragma unroll
-                for (int v = 1; v < 8; ++v) { m0 = gp_nanmax(m0, acc[i][j][v]); m1 = gp_nanmax(m1, acc[i][j][8 + v]); }
-                m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-                m1 = gp_nanmax(m1, __shfl_xor(m1, 32));
-                if (lane < 32) {
-                    const long g = rbase / 16;
-                    float r0 = m0 + bv, r1 = m1 + bv;
-                    if (relu) { r0 = r0 < 0.f ? 0.f : r0; r1 = r1 < 0.f ? 0.f : r1; }
-                    out[g * out_stride + col] = r0;
-                    out[(g + 1) * out_stride + col] = r1;
-                }
-            } else {
-                float m0 = acc[i][j][0];
-#pragma unroll
-                for (int v = 1; v < 16; ++v) m0 = gp_nanmax(m0, acc[i][j][v]);
-                m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-                if (lane < 32) {
-                    const long g = rbase / 32;
-                    float r0 = m0 + bv;
-                    if (relu) r0 = r0 < 0.f ? 0.f : r0;
-                    out[g * out_stride + col] = r0;
-                }
-            }
-        }
-}
-
-// XCD-aware tile order for the gather-GEMMs (1-D grid of col_tiles * row_tiles workgroups): workgroup g runs on XCD g % 8
-// (observed dispatch order).  With tps row tiles per scene and a batch that is a multiple of 8,
-//   scene = (g / 8 / (col_tiles * tps)) * 8 + g % 8,   row tile = (g / 8 / col_tiles) % tps,   col tile = (g / 8) % col_tiles
-// keeps (i) all tiles of a scene on ONE XCD -- the rows they gather (4 MB of features per scene at FP1) stay in that L2 instead
-// of being pulled through all eight -- and (ii) the col tiles of a row tile, which gather the SAME rows, next to each other on
-// that XCD (with the 2-D grid they ran on col_tiles different XCDs and each fetched the rows again).  tps = 0: plain order.
-__device__ __forceinline__ void gg_tile(int col_tiles, int tps, long &row_tile, int &col_tile, long g = -1) {
-    if (g < 0) g = blockIdx.x;
-    if (tps > 0) {
-        const long j = g >> 3;
-        col_tile = (int)(j % col_tiles);
-        const long jj = j / col_tiles;
-        row_tile = ((jj / tps) * 8 + (g & 7)) * tps + jj % tps;
-    } else {
-        col_tile = (int)(g % col_tiles);
-        row_tile = g / col_tiles;
-    }
+            pool_rows<NS>(w, acc[i][j], bias, relu, out, out_stride, row0 + sub_row<MB>(w, i), col0 + sub_col<NB, false>(w, j) + w.l32);
 }
 
 // ---- first SharedMLP layer of a set-abstraction scale with the GROUPING fused into its A operand:
@@ -262,73 +58,45 @@ __device__ __forceinline__ void gg_tile(int col_tiles, int tps, long &row_tile, 
 // i.e. QueryAndGroup (pointnet2_utils.py:241-264, channels-last, the xyz block behind the features: the caller
 // permutes the weight rows once) feeding layer 1 without the (rows, 3+C) grouped tensor ever existing: 156 MB per batch
 // written by the grouping kernel and read back by the GEMM at SA2, 102 MB at SA3.  Same 64 x 64 tile / LDS / MFMA
-// structure as gemm_pool_kernel; the X tile loader follows the neighbour list instead of a row pointer (a 16-byte load
+// structure as gemm_pool_big_kernel; the X tile loader follows the neighbour list instead of a row pointer (a 16-byte load
 // of 4 consecutive channels of the neighbour's feature row: C % 4 == 0 keeps it aligned and makes k == C a chunk start).
+struct GatherA {
+    const float *frow, *prow, *crow;
+    int c_feat;
+    // r: this thread's row of the tile, (scene, centre, sample) -> neighbour
+    __device__ __forceinline__ GatherA(long r, int c_feat_, int n, int m, int ns, const float *__restrict__ feats, const float *__restrict__ xyz,
+                                       const float *__restrict__ new_xyz, const int32_t *__restrict__ nbr) {
+        const long cm = r / ns;                                   // scene * m + centre
+        const long b = cm / m;
+        const int src = nbr[r];
+        frow = feats + ((size_t)b * n + (size_t)src) * c_feat_;
+        prow = xyz + ((size_t)b * n + (size_t)src) * 3;
+        crow = new_xyz + (size_t)cm * 3;
+        c_feat = c_feat_;
+    }
+    __device__ __forceinline__ float4 operator()(int, int k) const {
+        if (k < c_feat) return *reinterpret_cast<const float4 *>(frow + k);
+        if (k == c_feat) return make_float4(prow[0] - crow[0], prow[1] - crow[1], prow[2] - crow[2], 0.f);   // grouped_xyz -= new_xyz
+        return f4_zero();
+    }
+};
+
 __global__ __launch_bounds__(256) void gather_gemm_kernel(int c_feat, int o_dim, int n, int m, int ns, const float *__restrict__ feats,
                                                           const float *__restrict__ xyz, const float *__restrict__ new_xyz,
                                                           const int32_t *__restrict__ nbr, const float *__restrict__ wt,
                                                           const float *__restrict__ bias, int relu, float *__restrict__ out, int tps) {
-    __shared__ float xs[2][GP_KT][GP_XS];     // [k][row]
-    __shared__ float ws[2][GP_KT][64];        // [k][col]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
+    __shared__ float xs[2][GP_KT][GP_XS];                                       // [k][row]
+    __shared__ __attribute__((aligned(16))) float ws[2][GP_KT][64];             // [k][col]
+    const Wave w;
     long row_tile;
     int col_tile;
-    gg_tile(o_dim / 64, tps, row_tile, col_tile);
+    gg_tile<true>(o_dim / 64, tps, blockIdx.x, row_tile, col_tile);
     const long row0 = row_tile * 64;
     const int col0 = col_tile * 64;
-    const int k_dim = c_feat + 3;
-    const int xr = tid >> 2, xk = (tid & 3) * 4;
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    // this thread's row of the tile: (scene, centre, sample) -> neighbour
-    const long r = row0 + xr;
-    const long cm = r / ns;                                   // scene * m + centre
-    const long b = cm / m;
-    const int src = nbr[r];
-    const float *frow = feats + ((size_t)b * n + (size_t)src) * c_feat;
-    const float *prow = xyz + ((size_t)b * n + (size_t)src) * 3;
-    const float *crow = new_xyz + (size_t)cm * 3;
-    auto load_x = [&](int k0) {
-        const int k = k0 + xk;
-        if (k < c_feat) return *reinterpret_cast<const float4 *>(frow + k);
-        if (k == c_feat) return make_float4(prow[0] - crow[0], prow[1] - crow[1], prow[2] - crow[2], 0.f);   // grouped_xyz -= new_xyz
-        return make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto load_w = [&](int k0) {
-        const int k = k0 + wk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)k * o_dim + col0 + wc) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int buf, const float4 xv, const float4 wv) {
-        xs[buf][xk + 0][xr] = xv.x; xs[buf][xk + 1][xr] = xv.y; xs[buf][xk + 2][xr] = xv.z; xs[buf][xk + 3][xr] = xv.w;
-        *reinterpret_cast<float4 *>(&ws[buf][wk][wc]) = wv;
-    };
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 xv = load_x(0), wv = load_w(0);
-    stage(0, xv, wv);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) { xv = load_x((t + 1) * GP_KT); wv = load_w((t + 1) * GP_KT); }
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[cur][k + kh][ar], ws[cur][k + kh][bc], acc, 0, 0, 0);
-        if (t + 1 < ntiles) stage(cur ^ 1, xv, wv);
-        __syncthreads();
-    }
-    // accumulator layout (32 x 32 tile): register v of lane l holds row 8*(v/4) + 4*(l/32) + v%4, column l%32
-    const int col = col0 + bc;
-    const float bv = bias ? bias[col] : 0.f;
-    float *o = out + (row0 + wm * 32 + 4 * (lane >> 5)) * (long)o_dim + col;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        float y = acc[v] + bv;
-        if (relu) y = y < 0.f ? 0.f : y;       // NaN stays NaN, like relu_
-        o[(long)(8 * (v / 4) + (v % 4)) * o_dim] = y;
-    }
+    const GatherA load_a(row0 + (w.tid >> 2), c_feat, n, m, ns, feats, xyz, new_xyz, nbr);
+    floatx16 acc[1][1];
+    mfma_k_loop<1, 1, false>(w, acc, xs, ws, c_feat + 3, load_a, wt, o_dim, col0);
+    store_rows(w, acc[0][0], bias, relu, out, o_dim, row0 + w.wm * 32, col0 + w.bc);
 }
 
 // ---- the first TWO layers of a set-abstraction SharedMLP in one kernel: layer 1 as in gather_gemm_kernel (grouping fused into
@@ -336,219 +104,28 @@ __global__ __launch_bounds__(256) void gather_gemm_kernel(int c_feat, int o_dim,
 // bank conflicts and layer 2's A operand reads -- and layer 2 (O1 -> O2) multiplied straight out of it, 64 output columns at a
 // time.  Neither the grouped tensor nor the first activation (rows x O1) reaches HBM, and the rows of a tile are gathered once
 // instead of once per 64 output columns.  NB1 = O1 / 64 accumulators per wave in phase 1.
-// POOL = 16 | 32 (= ns): the THIRD layer and the pool over nsample follow in the same kernel -- layer 2's 64 x O2 tile goes to LDS
-// next to layer 1's instead of to HBM, layer 3 (O2 -> O3) is multiplied out of it 64 columns at a time and reduced over its row
-// groups in registers as in gemm_pool_kernel: of a whole SharedMLP only the pooled rows (rows / ns, O3) reach HBM.
-template <int NB1, int POOL = 0>
+template <int NB1>
 __global__ __launch_bounds__(256) void gather_gemm2_kernel(int c_feat, int o2, int n, int m, int ns, const float *__restrict__ feats,
                                                            const float *__restrict__ xyz, const float *__restrict__ new_xyz,
                                                            const int32_t *__restrict__ nbr, const float *__restrict__ w1t,
                                                            const float *__restrict__ b1, int relu1, const float *__restrict__ w2t,
-                                                           const float *__restrict__ b2, int relu2, float *__restrict__ out,
-                                                           int o3 = 0, const float *__restrict__ w3t = nullptr,
-                                                           const float *__restrict__ b3 = nullptr, int relu3 = 0, int out_stride = 0) {
+                                                           const float *__restrict__ b2, int relu2, float *__restrict__ out) {
     constexpr int O1 = NB1 * 64;
     extern __shared__ __attribute__((aligned(16))) float smem2[];
     // phase 1: xs[2][GP_KT][GP_XS] | w1s[2][GP_KT][O1];   phase 2 (aliases phase 1): act[O1][GP_XS] | w2s[2][GP_KT][64]
-    // with POOL: act[O1][GP_XS] | act2[O2P][GP_XS] | w2s[2][GP_KT][64],  O2P = o2 rounded up to the k-tile; layer 3's W tiles
-    // ([2][GP_KT][128]) reuse act
-    const int o2p = POOL ? (o2 + GP_KT - 1) / GP_KT * GP_KT : 0;
-    float *xs = smem2, *w1s = smem2 + 2 * GP_KT * GP_XS;
-    float *act = smem2, *act2 = smem2 + O1 * GP_XS, *w2s = smem2 + (O1 + o2p) * GP_XS;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
+    auto &xs = *reinterpret_cast<float (*)[2][GP_KT][GP_XS]>(smem2);
+    auto &w1s = *reinterpret_cast<float (*)[2][GP_KT][O1]>(smem2 + 2 * GP_KT * GP_XS);
+    float *act = smem2, *w2s = smem2 + O1 * GP_XS;
+    const Wave w;
     const long row0 = (long)blockIdx.x * 64;
-    const int k_dim = c_feat + 3;
-    const int xr = tid >> 2, xk = (tid & 3) * 4;
-    const long r = row0 + xr;
-    const long cm = r / ns;                                   // scene * m + centre
-    const long b = cm / m;
-    const int src = nbr[r];
-    const float *frow = feats + ((size_t)b * n + (size_t)src) * c_feat;
-    const float *prow = xyz + ((size_t)b * n + (size_t)src) * 3;
-    const float *crow = new_xyz + (size_t)cm * 3;
-    auto load_x = [&](int k0) {
-        const int k = k0 + xk;
-        if (k < c_feat) return *reinterpret_cast<const float4 *>(frow + k);
-        if (k == c_feat) return make_float4(prow[0] - crow[0], prow[1] - crow[1], prow[2] - crow[2], 0.f);   // grouped_xyz -= new_xyz
-        return make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    float4 wv[NB1];
-    auto load_w1 = [&](int k0) {
+    const GatherA load_a(row0 + (w.tid >> 2), c_feat, n, m, ns, feats, xyz, new_xyz, nbr);
+    floatx16 acc1[1][NB1];
+    mfma_k_loop<1, NB1, true>(w, acc1, xs, w1s, c_feat + 3, load_a, w1t, O1, 0);
 #pragma unroll
-        for (int j = 0; j < NB1; ++j) {
-            const int i = tid + 256 * j, k = k0 + i / (O1 / 4), c4 = i % (O1 / 4);
-            wv[j] = k < k_dim ? *reinterpret_cast<const float4 *>(w1t + (long)k * O1 + c4 * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stage1 = [&](int buf, const float4 xv) {
-        float *x = xs + buf * GP_KT * GP_XS;
-        x[(xk + 0) * GP_XS + xr] = xv.x; x[(xk + 1) * GP_XS + xr] = xv.y; x[(xk + 2) * GP_XS + xr] = xv.z; x[(xk + 3) * GP_XS + xr] = xv.w;
-#pragma unroll
-        for (int j = 0; j < NB1; ++j) {
-            const int i = tid + 256 * j;
-            *reinterpret_cast<float4 *>(w1s + buf * GP_KT * O1 + (i / (O1 / 4)) * O1 + (i % (O1 / 4)) * 4) = wv[j];
-        }
-    };
-    floatx16 acc1[NB1];
-#pragma unroll
-    for (int j = 0; j < NB1; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc1[j][i] = 0.f;
-    float4 xv = load_x(0);
-    load_w1(0);
-    stage1(0, xv);
-    __syncthreads();
-    const int nt1 = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < nt1; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < nt1) { xv = load_x((t + 1) * GP_KT); load_w1((t + 1) * GP_KT); }
-        const float *x = xs + cur * GP_KT * GP_XS, *wl = w1s + cur * GP_KT * O1;
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2) {
-            const float a = x[(k + kh) * GP_XS + ar];
-#pragma unroll
-            for (int j = 0; j < NB1; ++j) acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wl[(k + kh) * O1 + j * 64 + bc], acc1[j], 0, 0, 0);
-        }
-        if (t + 1 < nt1) stage1(cur ^ 1, xv);
-        __syncthreads();
-    }
-    // layer-1 epilogue into the activation tile (accumulator layout: register v of lane l = row 8*(v/4) + 4*(l/32) + v%4, column l%32)
-#pragma unroll
-    for (int j = 0; j < NB1; ++j) {
-        const int col = j * 64 + bc;
-        const float bv = b1 ? b1[col] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float y = acc1[j][v] + bv;
-            if (relu1) y = y < 0.f ? 0.f : y;
-            act[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * (lane >> 5) + (v % 4)] = y;
-        }
-    }
-    // layer 2, 64 output columns per pass; W2 tiles (16 x 64) double-buffered
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const int nchunk = (o2 + 63) / 64;
-    constexpr int nt2 = O1 / GP_KT;
-    for (int c = 0; c < nchunk; ++c) {
-        const int col0 = c * 64;
-        auto load_w2 = [&](int t) {
-            const int col = col0 + wc;      // o2 % 4 == 0: a float4 is inside or outside as a whole
-            return col < o2 ? *reinterpret_cast<const float4 *>(w2t + (long)(t * GP_KT + wk) * o2 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        floatx16 acc2;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
-        float4 w2v = load_w2(0);
-        __syncthreads();                    // the activation tile is complete / the previous pass has left w2s
-        *reinterpret_cast<float4 *>(w2s + wk * 64 + wc) = w2v;
-        __syncthreads();
-        for (int t = 0; t < nt2; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt2) w2v = load_w2(t + 1);
-            const float *wl = w2s + cur * GP_KT * 64;
-#pragma unroll
-            for (int k = 0; k < GP_KT; k += 2)
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(act[(t * GP_KT + k + kh) * GP_XS + ar], wl[(k + kh) * 64 + bc], acc2, 0, 0, 0);
-            if (t + 1 < nt2) *reinterpret_cast<float4 *>(w2s + (cur ^ 1) * GP_KT * 64 + wk * 64 + wc) = w2v;
-            __syncthreads();
-        }
-        const int col = col0 + bc;
-        if (POOL) {
-            if (col < o2p) {          // columns o2 .. o2p - 1: the zero padding of layer 3's k dimension
-                const float bv = (col < o2 && b2) ? b2[col] : 0.f;
-#pragma unroll
-                for (int v = 0; v < 16; ++v) {
-                    float y = acc2[v] + bv;
-                    if (relu2) y = y < 0.f ? 0.f : y;
-                    act2[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * (lane >> 5) + (v % 4)] = col < o2 ? y : 0.f;
-                }
-            }
-        } else if (col < o2) {
-            const float bv = b2 ? b2[col] : 0.f;
-            float *o = out + (row0 + wm * 32 + 4 * (lane >> 5)) * (long)o2 + col;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                float y = acc2[v] + bv;
-                if (relu2) y = y < 0.f ? 0.f : y;
-                o[(long)(8 * (v / 4) + (v % 4)) * o2] = y;
-            }
-        }
-    }
-    if (POOL) {
-        // layer 3 out of act2, 128 output columns per pass (o3 % 128 == 0; two accumulators per wave: half the barriers and
-        // half the reads of the activation of a 64-column pass), then the max over each group of POOL rows
-        const int nt3 = o2p / GP_KT;
-        const int wk3 = tid >> 5, wc3 = (tid & 31) * 4;          // W3 tile 16 x 128: two float4 per thread (rows wk3, wk3 + 8)
-        float *w3s = smem2;                                      // [2][GP_KT][128] in layer 1's activation tile, which is dead by now (O1 * GP_XS >= 4096)
-        for (int c = 0; c < o3 / 128; ++c) {
-            const int col0 = c * 128;
-            float4 w3v[2];
-            auto load_w3 = [&](int t) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int k = t * GP_KT + wk3 + 8 * q;
-                    w3v[q] = k < o2 ? *reinterpret_cast<const float4 *>(w3t + (long)k * o3 + col0 + wc3) : make_float4(0.f, 0.f, 0.f, 0.f);
-                }
-            };
-            auto stage_w3 = [&](int buf) {
-#pragma unroll
-                for (int q = 0; q < 2; ++q) *reinterpret_cast<float4 *>(w3s + buf * GP_KT * 128 + (wk3 + 8 * q) * 128 + wc3) = w3v[q];
-            };
-            floatx16 acc3[2];
-#pragma unroll
-            for (int q = 0; q < 2; ++q)
-#pragma unroll
-                for (int i = 0; i < 16; ++i) acc3[q][i] = 0.f;
-            load_w3(0);
-            __syncthreads();                // act2 is complete, act is dead / the previous pass has left w3s
-            stage_w3(0);
-            __syncthreads();
-            for (int t = 0; t < nt3; ++t) {
-                const int cur = t & 1;
-                if (t + 1 < nt3) load_w3(t + 1);
-                const float *wl = w3s + cur * GP_KT * 128;
-#pragma unroll
-                for (int k = 0; k < GP_KT; k += 2) {
-                    const float a = act2[(t * GP_KT + k + kh) * GP_XS + ar];
-#pragma unroll
-                    for (int q = 0; q < 2; ++q) acc3[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wl[(k + kh) * 128 + q * 64 + bc], acc3[q], 0, 0, 0);
-                }
-                if (t + 1 < nt3) stage_w3(cur ^ 1);
-                __syncthreads();
-            }
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int col = col0 + q * 64 + bc;
-                const float bv = b3 ? b3[col] : 0.f;
-                if (POOL == 16) {
-                    float m0 = acc3[q][0], m1 = acc3[q][8];
-#pragma unroll
-                    for (int v = 1; v < 8; ++v) { m0 = gp_nanmax(m0, acc3[q][v]); m1 = gp_nanmax(m1, acc3[q][8 + v]); }
-                    m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-                    m1 = gp_nanmax(m1, __shfl_xor(m1, 32));
-                    if (lane < 32) {
-                        const long g = (row0 + wm * 32) / 16;
-                        float r0 = m0 + bv, r1 = m1 + bv;
-                        if (relu3) { r0 = r0 < 0.f ? 0.f : r0; r1 = r1 < 0.f ? 0.f : r1; }
-                        out[g * out_stride + col] = r0;
-                        out[(g + 1) * out_stride + col] = r1;
-                    }
-                } else {
-                    float m0 = acc3[q][0];
-#pragma unroll
-                    for (int v = 1; v < 16; ++v) m0 = gp_nanmax(m0, acc3[q][v]);
-                    m0 = gp_nanmax(m0, __shfl_xor(m0, 32));
-                    if (lane < 32) {
-                        const long g = (row0 + wm * 32) / 32;
-                        float r0 = m0 + bv;
-                        if (relu3) r0 = r0 < 0.f ? 0.f : r0;
-                        out[g * out_stride + col] = r0;
-                    }
-                }
-            }
-        }
-    }
+    for (int j = 0; j < NB1; ++j) store_act(w, acc1[0][j], b1, relu1, act, j * 64 + w.bc);
+    lds_layer<1>(w, act, O1 / GP_KT, w2t, O1, o2, w2s, 0, 1, [&](const floatx16 &acc, int col) __attribute__((always_inline)) {
+        if (col < o2) store_rows(w, acc, b2, relu2, out, o2, row0 + w.wm * 32, col);
+    });
 }
 
 // ---- layer 1 of a set-abstraction SharedMLP WITHOUT its per-pair product.  The layer is linear in the grouped row,
@@ -557,8 +134,8 @@ __global__ __launch_bounds__(256) void gather_gemm2_kernel(int c_feat, int o2, i
 // product over its m * ns (centre, sample) pairs -- 12 x fewer rows at SA2..SA4 (ns = 16 + 32 pairs per centre, n = 4 m), i.e.
 // 15 % of all the fp32 matrix work of the network.  What is left per pair is a gather of P's row (O1 floats instead of the C
 // feature channels: half the bytes), the three-term xyz product -- kept in the centred form, so nothing cancels -- bias and ReLU.
-// pgather_gemm2_kernel: that, feeding layer 2 as in gather_gemm2_kernel (the accumulators of layer 1 START at the gathered P
-// values and take two matrix steps for [dx dy dz 0]); pgather_rows_kernel: layer 1 alone (rows x O1), for the widest level.
+// pgather_gemm2_kernel: that (ppoint_layer1 of mfma_tile.h), feeding layer 2 as in gather_gemm2_kernel; pgather_rows_kernel:
+// layer 1 alone (rows x O1), for the widest level.
 template <int NB1>
 __global__ __launch_bounds__(256) void pgather_gemm2_kernel(int o2, int n, int m, int ns, const float *__restrict__ pmat, int p_stride,
                                                             const float *__restrict__ xyz, const float *__restrict__ new_xyz,
@@ -570,85 +147,13 @@ __global__ __launch_bounds__(256) void pgather_gemm2_kernel(int o2, int n, int m
     constexpr int O1 = NB1 * 64;
     extern __shared__ __attribute__((aligned(16))) float smem2[];
     float *act = smem2, *w2s = smem2 + O1 * GP_XS;           // act[O1][GP_XS] | w2s[2][GP_KT][64]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
+    const Wave w;
     const long row0 = (long)blockIdx.x * 64;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
     const long scene = row0 / ((long)m * ns);               // a 64-row tile lies inside one scene (m * ns % 64 == 0)
-    // this lane's row of the A operand: the centred coordinates, k = 0..3 -> (dx, dy | dz, 0) over the two halves of the wave
-    float a0, a1;
-    {
-        const long r = row0 + ar;
-        const long cm = r / ns;
-        const int src = nbr[r];
-        const float *pr = xyz + ((size_t)scene * n + (size_t)src) * 3, *cr = new_xyz + (size_t)cm * 3;
-        const float dx = pr[0] - cr[0], dy = pr[1] - cr[1], dz = pr[2] - cr[2];
-        a0 = kh ? dy : dx;
-        a1 = kh ? 0.f : dz;
-    }
-    // accumulators start at P[source point of the row][column]: register v of lane l = row 8 (v / 4) + 4 (l / 32) + v % 4
-    floatx16 acc1[NB1];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const int src = nbr[row0 + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4)];
-        const float *prow = pmat + ((size_t)scene * n + (size_t)src) * p_stride + bc;
-#pragma unroll
-        for (int j = 0; j < NB1; ++j) acc1[j][v] = prow[j * 64];
-    }
-#pragma unroll
-    for (int j = 0; j < NB1; ++j) {
-        const int col = j * 64 + bc;
-        const float wb0 = w1x[kh * O1 + col];                         // k = 0 | 1: the x | y row of W_x
-        const float wb1 = kh ? 0.f : w1x[2 * O1 + col];               // k = 2 | 3: the z row | the zero pad
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, wb0, acc1[j], 0, 0, 0);
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, wb1, acc1[j], 0, 0, 0);
-        const float bv = b1 ? b1[col] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float y = acc1[j][v] + bv;
-            if (relu1) y = y < 0.f ? 0.f : y;
-            act[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4)] = y;
-        }
-    }
-    // layer 2, 64 output columns per pass; W2 tiles (16 x 64) double-buffered (as in gather_gemm2_kernel)
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const int nchunk = (o2 + 63) / 64;
-    constexpr int nt2 = O1 / GP_KT;
-    for (int c = 0; c < nchunk; ++c) {
-        const int col0 = c * 64;
-        auto load_w2 = [&](int t) {
-            const int col = col0 + wc;      // o2 % 4 == 0: a float4 is inside or outside as a whole
-            return col < o2 ? *reinterpret_cast<const float4 *>(w2t + (long)(t * GP_KT + wk) * o2 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        floatx16 acc2;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
-        float4 w2v = load_w2(0);
-        __syncthreads();                    // the activation tile is complete / the previous pass has left w2s
-        *reinterpret_cast<float4 *>(w2s + wk * 64 + wc) = w2v;
-        __syncthreads();
-        for (int t = 0; t < nt2; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt2) w2v = load_w2(t + 1);
-            const float *wl = w2s + cur * GP_KT * 64;
-#pragma unroll
-            for (int k = 0; k < GP_KT; k += 2)
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(act[(t * GP_KT + k + kh) * GP_XS + ar], wl[(k + kh) * 64 + bc], acc2, 0, 0, 0);
-            if (t + 1 < nt2) *reinterpret_cast<float4 *>(w2s + (cur ^ 1) * GP_KT * 64 + wk * 64 + wc) = w2v;
-            __syncthreads();
-        }
-        const int col = col0 + bc;
-        if (col < o2) {
-            const float bv = b2 ? b2[col] : 0.f;
-            float *o = out + (row0 + wm * 32 + 4 * kh) * (long)o2 + col;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                float y = acc2[v] + bv;
-                if (relu2) y = y < 0.f ? 0.f : y;
-                o[(long)(8 * (v / 4) + (v % 4)) * o2] = y;
-            }
-        }
-    }
+    ppoint_layer1<NB1>(w, [&](int tr) __attribute__((always_inline)) { return PairRow{scene, (row0 + tr) / ns, nbr[row0 + tr]}; }, n, pmat, p_stride, xyz, new_xyz, w1x, b1, relu1, act);
+    lds_layer<1>(w, act, O1 / GP_KT, w2t, O1, o2, w2s, 0, 1, [&](const floatx16 &acc, int col) __attribute__((always_inline)) {
+        if (col < o2) store_rows(w, acc, b2, relu2, out, o2, row0 + w.wm * 32, col);
+    });
 }
 
 // layer 1 alone: out[r, :] = relu?( P[source of r, :] + W_x (x - c) + b1 ); 64 threads x float4 per 256 columns, rows walked
@@ -740,7 +245,20 @@ __global__ __launch_bounds__(256) void pair_compact_kernel(long centres, int ns,
     }
 }
 
-// pgather_gemm2_kernel over compact rows: (centre, source) per row from rowc / rowsrc, *total rows in all
+// (centre, source) of tile row tr of the compact tile that starts at row0: from rowc / rowsrc, *total = T rows in all; rows behind
+// the end repeat the last one (never stored or reduced)
+struct CompactSrc {
+    const int32_t *__restrict__ rowc, *__restrict__ rowsrc;
+    long row0, T;
+    int m;
+    __device__ __forceinline__ PairRow operator()(int tr) const {
+        const long t = min(row0 + tr, T - 1);
+        const int cm = rowc[t];
+        return PairRow{cm / m, cm, rowsrc[t]};
+    }
+};
+
+// pgather_gemm2_kernel over compact rows
 template <int NB1>
 __device__ __forceinline__ void pgather_gemm2_compact_body(const unsigned bx, const unsigned by, const unsigned gy, int o2, int n, int m,
                                                            const float *__restrict__ pmat, int p_stride,
@@ -755,83 +273,13 @@ __device__ __forceinline__ void pgather_gemm2_compact_body(const unsigned bx, co
     if (row0 >= T || (limit >= 0 && T > limit)) return;      // workgroup-uniform; beyond the limit the dense kernels run instead
     extern __shared__ __attribute__((aligned(16))) float smem2[];
     float *act = smem2, *w2s = smem2 + O1 * GP_XS;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    float a0, a1;
-    {
-        const long t = min(row0 + ar, T - 1);                // rows behind the end repeat the last one (never stored)
-        const long cm = rowc[t];
-        const long scene = cm / m;
-        const int src = rowsrc[t];
-        const float *pr = xyz + ((size_t)scene * n + (size_t)src) * 3, *cr = new_xyz + (size_t)cm * 3;
-        const float dx = pr[0] - cr[0], dy = pr[1] - cr[1], dz = pr[2] - cr[2];
-        a0 = kh ? dy : dx;
-        a1 = kh ? 0.f : dz;
-    }
-    floatx16 acc1[NB1];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const long t = min(row0 + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4), T - 1);
-        const long scene = rowc[t] / m;
-        const float *prow = pmat + ((size_t)scene * n + (size_t)rowsrc[t]) * p_stride + bc;
-#pragma unroll
-        for (int j = 0; j < NB1; ++j) acc1[j][v] = prow[j * 64];
-    }
-#pragma unroll
-    for (int j = 0; j < NB1; ++j) {
-        const int col = j * 64 + bc;
-        const float wb0 = w1x[kh * O1 + col];
-        const float wb1 = kh ? 0.f : w1x[2 * O1 + col];
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, wb0, acc1[j], 0, 0, 0);
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, wb1, acc1[j], 0, 0, 0);
-        const float bv = b1 ? b1[col] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float y = acc1[j][v] + bv;
-            if (relu1) y = y < 0.f ? 0.f : y;
-            act[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4)] = y;
-        }
-    }
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const int nchunk = (o2 + 63) / 64;
-    constexpr int nt2 = O1 / GP_KT;
-    for (int c = by; c < nchunk; c += gy) {       // the 64-column passes of layer 2 are spread over gridDim.y workgroups (each
-        const int col0 = c * 64;                                   // rebuilds layer 1's tile: a gather and two matrix steps): compact launches are small
-        auto load_w2 = [&](int t) {
-            const int col = col0 + wc;
-            return col < o2 ? *reinterpret_cast<const float4 *>(w2t + (long)(t * GP_KT + wk) * o2 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        floatx16 acc2;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
-        float4 w2v = load_w2(0);
-        __syncthreads();
-        *reinterpret_cast<float4 *>(w2s + wk * 64 + wc) = w2v;
-        __syncthreads();
-        for (int t = 0; t < nt2; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt2) w2v = load_w2(t + 1);
-            const float *wl = w2s + cur * GP_KT * 64;
-#pragma unroll
-            for (int k = 0; k < GP_KT; k += 2)
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(act[(t * GP_KT + k + kh) * GP_XS + ar], wl[(k + kh) * 64 + bc], acc2, 0, 0, 0);
-            if (t + 1 < nt2) *reinterpret_cast<float4 *>(w2s + (cur ^ 1) * GP_KT * 64 + wk * 64 + wc) = w2v;
-            __syncthreads();
-        }
-        const int col = col0 + bc;
-        if (col < o2) {
-            const float bv = b2 ? b2[col] : 0.f;
-            const long rb = row0 + wm * 32 + 4 * kh;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                const long t = rb + 8 * (v / 4) + (v % 4);
-                float y = acc2[v] + bv;
-                if (relu2) y = y < 0.f ? 0.f : y;
-                if (t < T) out[t * (long)o2 + col] = y;
-            }
-        }
-    }
+    const Wave w;
+    ppoint_layer1<NB1>(w, CompactSrc{rowc, rowsrc, row0, T, m}, n, pmat, p_stride, xyz, new_xyz, w1x, b1, relu1, act);
+    // the 64-column passes of layer 2 are spread over gridDim.y workgroups (each rebuilds layer 1's tile: a gather and two matrix
+    // steps): compact launches are small
+    lds_layer<1>(w, act, O1 / GP_KT, w2t, O1, o2, w2s, (int)by, (int)gy, [&](const floatx16 &acc, int col) __attribute__((always_inline)) {
+        if (col < o2) store_rows(w, acc, b2, relu2, out, o2, row0 + w.wm * 32, col, T);
+    });
 }
 
 template <int NB1>
@@ -885,48 +333,17 @@ __device__ __forceinline__ void gemm_pool_compact_body(const unsigned bx, int k_
     const long row0 = row_tile * 64;
     if (row0 >= T || (limit >= 0 && T > limit)) return;
     __shared__ float xs[2][GP_KT][GP_XS];
-    __shared__ float ws[2][GP_KT][64];
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
+    __shared__ __attribute__((aligned(16))) float ws[2][GP_KT][64];
+    const Wave w;
     const int col0 = col_tile * 64;
-    const int xr = tid >> 2, xk = (tid & 3) * 4;
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const float *xp = x + min(row0 + xr, T - 1) * (long)k_dim;
-    auto load_x = [&](int k0) {
-        const int k = k0 + xk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(xp + k) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto load_w = [&](int k0) {
-        const int k = k0 + wk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)k * o_dim + col0 + wc) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int buf, const float4 xv, const float4 wv) {
-        xs[buf][xk + 0][xr] = xv.x; xs[buf][xk + 1][xr] = xv.y; xs[buf][xk + 2][xr] = xv.z; xs[buf][xk + 3][xr] = xv.w;
-        *reinterpret_cast<float4 *>(&ws[buf][wk][wc]) = wv;
-    };
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 xv = load_x(0), wv = load_w(0);
-    stage(0, xv, wv);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) { xv = load_x((t + 1) * GP_KT); wv = load_w((t + 1) * GP_KT); }
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[cur][k + kh][ar], ws[cur][k + kh][bc], acc, 0, 0, 0);
-        if (t + 1 < ntiles) stage(cur ^ 1, xv, wv);
-        __syncthreads();
-    }
-    const int col = col0 + bc;
-    const float bv = bias ? bias[col] : 0.f;
+    const RowsA<1> load_a{{x + min(row0 + (w.tid >> 2), T - 1) * (long)k_dim}, k_dim};
+    floatx16 acc[1][1];
+    mfma_k_loop<1, 1, false>(w, acc, xs, ws, k_dim, load_a, wt, o_dim, col0);
+    const int col = col0 + w.bc;
     // consecutive rows mostly belong to one centre: each half pools 16 consecutive rows in registers, one atomic per centre (compact_pool.h)
     int cen[16];
-    compact_centres16(rowc, row0 + wm * 32 + 16 * kh, T, cen);
-    compact_pool_atomic(acc, bv, cen, out + col, out_stride);
+    compact_centres16(rowc, row0 + w.wm * 32 + 16 * w.kh, T, cen);
+    compact_pool_atomic(acc[0][0], bias ? bias[col] : 0.f, cen, out + col, out_stride);
 }
 
 __global__ __launch_bounds__(256) void gemm_pool_compact_kernel(int k_dim, int o_dim, const float *__restrict__ x, const int32_t *__restrict__ rowc,
@@ -945,8 +362,8 @@ __global__ __launch_bounds__(256) void gemm_pool_compact_pair_kernel(const Compa
 }
 
 // ---- the WHOLE SharedMLP of a set-abstraction scale over compact rows in one kernel (round 4): pgather_gemm2_compact_kernel's
-// layer 1 (gathered P row + xyz term) and layer 2, layer 2's 64 x O2 tile kept in LDS next to layer 1's (as gather_gemm2_kernel<.., POOL>
-// does for dense rows) and gemm_pool_compact_kernel's last layer + atomic max multiplied straight out of it, 128 output columns per
+// layer 1 (gathered P row + xyz term) and layer 2, layer 2's 64 x O2 tile kept in LDS next to layer 1's (instead of going to HBM)
+// and gemm_pool_compact_kernel's last layer + atomic max multiplied straight out of it, 128 output columns per
 // pass.  Against the two-kernel form: the (rows, O2) activation never reaches HBM (98 MB per batch of 8 at SA2, written and read
 // back), the rows of a tile are gathered once instead of once per 64-column pass of layer 2, one launch per scale instead of two.
 // The k order of every dot product is the two kernels' (ascending k, two per matrix instruction, zero padding behind o2): the
@@ -964,135 +381,22 @@ __device__ __forceinline__ void pgather_gemm3_compact_body(const unsigned bx, in
     const long row0 = (long)bx * 64;
     if (row0 >= T || (limit >= 0 && T > limit)) return;      // workgroup-uniform; beyond the limit the dense kernels run instead
     extern __shared__ __attribute__((aligned(16))) float smem2[];
+    // act[O1][GP_XS] | act2[O2P][GP_XS] | w2s[2][GP_KT][64],  O2P = o2 rounded up to the k-tile
     const int o2p = (o2 + GP_KT - 1) / GP_KT * GP_KT;
     float *act = smem2, *act2 = smem2 + O1 * GP_XS, *w2s = smem2 + (O1 + o2p) * GP_XS;
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    float a0, a1;
-    {
-        const long t = min(row0 + ar, T - 1);                // rows behind the end repeat the last one (never reduced)
-        const long cm = rowc[t];
-        const long scene = cm / m;
-        const int src = rowsrc[t];
-        const float *pr = xyz + ((size_t)scene * n + (size_t)src) * 3, *cr = new_xyz + (size_t)cm * 3;
-        const float dx = pr[0] - cr[0], dy = pr[1] - cr[1], dz = pr[2] - cr[2];
-        a0 = kh ? dy : dx;
-        a1 = kh ? 0.f : dz;
-    }
+    const Wave w;
     int cidx[16];                                            // the centres of the 16 consecutive rows this half pools (compact_pool.h)
-    compact_centres16(rowc, row0 + wm * 32 + 16 * kh, T, cidx);
-    floatx16 acc1[NB1];
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        const long tr = row0 + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4);
-        const long t = min(tr, T - 1);
-        const int cm = rowc[t];
-        const long scene = cm / m;
-        const float *prow = pmat + ((size_t)scene * n + (size_t)rowsrc[t]) * p_stride + bc;
-#pragma unroll
-        for (int j = 0; j < NB1; ++j) acc1[j][v] = prow[j * 64];
-    }
-#pragma unroll
-    for (int j = 0; j < NB1; ++j) {
-        const int col = j * 64 + bc;
-        const float wb0 = w1x[kh * O1 + col];
-        const float wb1 = kh ? 0.f : w1x[2 * O1 + col];
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, wb0, acc1[j], 0, 0, 0);
-        acc1[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, wb1, acc1[j], 0, 0, 0);
-        const float bv = b1 ? b1[col] : 0.f;
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            float y = acc1[j][v] + bv;
-            if (relu1) y = y < 0.f ? 0.f : y;
-            act[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4)] = y;
-        }
-    }
-    // layer 2 into act2, 64 output columns per pass
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const int nchunk = (o2 + 63) / 64;
-    constexpr int nt2 = O1 / GP_KT;
-    for (int c = 0; c < nchunk; ++c) {
-        const int col0 = c * 64;
-        auto load_w2 = [&](int t) {
-            const int col = col0 + wc;
-            return col < o2 ? *reinterpret_cast<const float4 *>(w2t + (long)(t * GP_KT + wk) * o2 + col) : make_float4(0.f, 0.f, 0.f, 0.f);
-        };
-        floatx16 acc2;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
-        float4 w2v = load_w2(0);
-        __syncthreads();                    // the activation tile is complete / the previous pass has left w2s
-        *reinterpret_cast<float4 *>(w2s + wk * 64 + wc) = w2v;
-        __syncthreads();
-        for (int t = 0; t < nt2; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt2) w2v = load_w2(t + 1);
-            const float *wl = w2s + cur * GP_KT * 64;
-#pragma unroll
-            for (int k = 0; k < GP_KT; k += 2)
-                acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(act[(t * GP_KT + k + kh) * GP_XS + ar], wl[(k + kh) * 64 + bc], acc2, 0, 0, 0);
-            if (t + 1 < nt2) *reinterpret_cast<float4 *>(w2s + (cur ^ 1) * GP_KT * 64 + wk * 64 + wc) = w2v;
-            __syncthreads();
-        }
-        const int col = col0 + bc;
-        if (col < o2p) {                    // columns o2 .. o2p - 1: the zero padding of layer 3's k dimension
-            const float bv = (col < o2 && b2) ? b2[col] : 0.f;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                float y = acc2[v] + bv;
-                if (relu2) y = y < 0.f ? 0.f : y;
-                act2[col * GP_XS + wm * 32 + 8 * (v / 4) + 4 * kh + (v % 4)] = col < o2 ? y : 0.f;
-            }
-        }
-    }
-    // layer 3 out of act2, 128 output columns per pass (o3 % 128 == 0), W3 tiles ([2][GP_KT][128]) in layer 1's tile, which is dead by now
-    const int nt3 = o2p / GP_KT;
-    const int wk3 = tid >> 5, wc3 = (tid & 31) * 4;
-    float *w3s = smem2;
-    for (int c = 0; c < o3 / 128; ++c) {
-        const int col0 = c * 128;
-        float4 w3v[2];
-        auto load_w3 = [&](int t) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) {
-                const int k = t * GP_KT + wk3 + 8 * q;
-                w3v[q] = k < o2 ? *reinterpret_cast<const float4 *>(w3t + (long)k * o3 + col0 + wc3) : make_float4(0.f, 0.f, 0.f, 0.f);
-            }
-        };
-        auto stage_w3 = [&](int buf) {
-#pragma unroll
-            for (int q = 0; q < 2; ++q) *reinterpret_cast<float4 *>(w3s + buf * GP_KT * 128 + (wk3 + 8 * q) * 128 + wc3) = w3v[q];
-        };
-        floatx16 acc3[2];
-#pragma unroll
-        for (int q = 0; q < 2; ++q)
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc3[q][i] = 0.f;
-        load_w3(0);
-        __syncthreads();                    // act2 is complete, act is dead / the previous pass has left w3s
-        stage_w3(0);
-        __syncthreads();
-        for (int t = 0; t < nt3; ++t) {
-            const int cur = t & 1;
-            if (t + 1 < nt3) load_w3(t + 1);
-            const float *wl = w3s + cur * GP_KT * 128;
-#pragma unroll
-            for (int k = 0; k < GP_KT; k += 2) {
-                const float a = act2[(t * GP_KT + k + kh) * GP_XS + ar];
-#pragma unroll
-                for (int q = 0; q < 2; ++q) acc3[q] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, wl[(k + kh) * 128 + q * 64 + bc], acc3[q], 0, 0, 0);
-            }
-            if (t + 1 < nt3) stage_w3(cur ^ 1);
-            __syncthreads();
-        }
-        // bias + ReLU, each half pools its 16 consecutive rows, one integer atomic max per centre (compact_pool.h)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-            const int col = col0 + q * 64 + bc;
-            compact_pool_atomic(acc3[q], b3 ? b3[col] : 0.f, cidx, out + col, out_stride);
-        }
-    }
+    compact_centres16(rowc, row0 + w.wm * 32 + 16 * w.kh, T, cidx);
+    ppoint_layer1<NB1>(w, CompactSrc{rowc, rowsrc, row0, T, m}, n, pmat, p_stride, xyz, new_xyz, w1x, b1, relu1, act);
+    // layer 2 into act2, 64 output columns per pass; columns o2 .. o2p - 1: the zero padding of layer 3's k dimension
+    lds_layer<1>(w, act, O1 / GP_KT, w2t, O1, o2, w2s, 0, 1, [&](const floatx16 &acc, int col) __attribute__((always_inline)) {
+        if (col < o2p) store_act(w, acc, b2, relu2, act2, col, o2);
+    });
+    // layer 3 out of act2, 128 output columns per pass (o3 % 128 == 0), W3 tiles ([2][GP_KT][128]) in layer 1's tile, which is dead
+    // by now (O1 * GP_XS >= 4096); bias + ReLU, each half pools its 16 consecutive rows, one integer atomic max per centre
+    lds_layer<2>(w, act2, o2p / GP_KT, w3t, o2, o3, smem2, 0, 1, [&](const floatx16 &acc, int col) __attribute__((always_inline)) {
+        compact_pool_atomic(acc, b3 ? b3[col] : 0.f, cidx, out + col, out_stride);
+    });
 }
 
 template <int NB1>
@@ -1115,13 +419,39 @@ __global__ __launch_bounds__(256) void pgather_gemm3_compact_pair_kernel(const C
                                     a.w1x, a.b1, a.relu1, a.w2t, a.b2, a.relu2, a.w3t, a.b3, a.out, a.out_stride, a.limit);
 }
 
+// three_interpolate's expression (interpolate_gpu.cu:77-97) on four channels, and the small float4 helpers of the FP kernels
+__device__ __forceinline__ float4 interp3(float w0, const float4 p0, float w1, const float4 p1, float w2, const float4 p2) {
+    return make_float4(__builtin_fmaf(w2, p2.x, __builtin_fmaf(w0, p0.x, w1 * p1.x)), __builtin_fmaf(w2, p2.y, __builtin_fmaf(w0, p0.y, w1 * p1.y)),
+                       __builtin_fmaf(w2, p2.z, __builtin_fmaf(w0, p0.z, w1 * p1.z)), __builtin_fmaf(w2, p2.w, __builtin_fmaf(w0, p0.w, w1 * p1.w)));
+}
+__device__ __forceinline__ float4 ld4(const float *p) { return *reinterpret_cast<const float4 *>(p); }
+__device__ __forceinline__ void add4(float4 &y, const float4 a) { y.x += a.x; y.y += a.y; y.z += a.z; y.w += a.w; }
+__device__ __forceinline__ void fma4(float4 &y, float s, const float4 a) {
+    y.x = __builtin_fmaf(s, a.x, y.x); y.y = __builtin_fmaf(s, a.y, y.y); y.z = __builtin_fmaf(s, a.z, y.z); y.w = __builtin_fmaf(s, a.w, y.w);
+}
+__device__ __forceinline__ void relu4(float4 &y) { y.x = y.x < 0.f ? 0.f : y.x; y.y = y.y < 0.f ? 0.f : y.y; y.z = y.z < 0.f ? 0.f : y.z; y.w = y.w < 0.f ? 0.f : y.w; }
+
 // ---- first layer of a feature-propagation module WITHOUT its per-point product over the interpolated channels.  Interpolation
 // is linear, so  W_a (w0 f[i0] + w1 f[i1] + w2 f[i2]) = w0 (W_a f)[i0] + w1 (W_a f)[i1] + w2 (W_a f)[i2]:  Q = known_feats @ W_a
 // is one product over the m KNOWN points (a quarter of the unknown ones), and the layer is
 //   out[r, :] = relu?( w0 Q[i0, :] + w1 Q[i1, :] + w2 Q[i2, :] + lin[r, :] ),   lin = skip @ W_b + bias
 // where lin comes from a GEMM over the skip channels only (lin != NULL), or -- c1 <= 4 skip channels (FP1: one) -- is
 // evaluated here as fmaf chains over skip[r, 0:c1] and wb (c1, o).  The interpolation uses three_interpolate's expression
-// (interpolate_gpu.cu:77-97) on Q's rows.  One float4 of a row per thread.
+// (interp3) on Q's rows.  qrow_f4: channels k .. k + 3 of one row, given the row's three (Q row, weight) pairs.
+__device__ __forceinline__ float4 qrow_f4(int k, int o, const float *q0, const float *q1, const float *q2, float w0, float w1, float w2,
+                                          const float *lrow, const float *srow, int c1, const float *__restrict__ wb, const float *__restrict__ bias, int relu) {
+    float4 y = interp3(w0, ld4(q0 + k), w1, ld4(q1 + k), w2, ld4(q2 + k));
+    if (lrow) {
+        add4(y, ld4(lrow + k));
+    } else {
+        for (int j = 0; j < c1; ++j) fma4(y, srow[j], ld4(wb + (long)j * o + k));
+        if (bias) add4(y, ld4(bias + k));
+    }
+    if (relu) relu4(y);
+    return y;
+}
+
+// One float4 of a row per thread.
 __global__ __launch_bounds__(256) void qinterp_rows_kernel(long rows, int o, int n, int m, const float *__restrict__ q, const int32_t *__restrict__ idx3,
                                                            const float *__restrict__ w3, const float *__restrict__ lin,
                                                            const float *__restrict__ skip, int c1, const float *__restrict__ wb,
@@ -1131,114 +461,93 @@ __global__ __launch_bounds__(256) void qinterp_rows_kernel(long rows, int o, int
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
         const long r = e / q4;
         const int c4 = (int)(e - r * q4) * 4;
-        const long scene = r / n;
-        const int i0 = idx3[r * 3 + 0], i1 = idx3[r * 3 + 1], i2 = idx3[r * 3 + 2];
-        const float w0 = w3[r * 3 + 0], w1 = w3[r * 3 + 1], w2 = w3[r * 3 + 2];
-        const float *qb = q + (size_t)scene * m * o + c4;
-        const float4 p0 = *reinterpret_cast<const float4 *>(qb + (size_t)i0 * o), p1 = *reinterpret_cast<const float4 *>(qb + (size_t)i1 * o),
-                     p2 = *reinterpret_cast<const float4 *>(qb + (size_t)i2 * o);
-        float4 y = make_float4(__builtin_fmaf(w2, p2.x, __builtin_fmaf(w0, p0.x, w1 * p1.x)), __builtin_fmaf(w2, p2.y, __builtin_fmaf(w0, p0.y, w1 * p1.y)),
-                               __builtin_fmaf(w2, p2.z, __builtin_fmaf(w0, p0.z, w1 * p1.z)), __builtin_fmaf(w2, p2.w, __builtin_fmaf(w0, p0.w, w1 * p1.w)));
-        if (lin) {
-            const float4 l4 = *reinterpret_cast<const float4 *>(lin + r * (long)o + c4);
-            y.x += l4.x; y.y += l4.y; y.z += l4.z; y.w += l4.w;
-        } else {
-            for (int k = 0; k < c1; ++k) {
-                const float sv = skip[r * (long)c1 + k];
-                const float4 wv = *reinterpret_cast<const float4 *>(wb + (long)k * o + c4);
-                y.x = __builtin_fmaf(sv, wv.x, y.x); y.y = __builtin_fmaf(sv, wv.y, y.y); y.z = __builtin_fmaf(sv, wv.z, y.z); y.w = __builtin_fmaf(sv, wv.w, y.w);
-            }
-            if (bias) {
-                const float4 bv = *reinterpret_cast<const float4 *>(bias + c4);
-                y.x += bv.x; y.y += bv.y; y.z += bv.z; y.w += bv.w;
-            }
-        }
-        if (relu) { y.x = y.x < 0.f ? 0.f : y.x; y.y = y.y < 0.f ? 0.f : y.y; y.z = y.z < 0.f ? 0.f : y.z; y.w = y.w < 0.f ? 0.f : y.w; }
-        *reinterpret_cast<float4 *>(out + r * (long)o + c4) = y;
+        const float *qb = q + (size_t)(r / n) * m * o;
+        *reinterpret_cast<float4 *>(out + r * (long)o + c4) =
+            qrow_f4(c4, o, qb + (size_t)idx3[r * 3 + 0] * o, qb + (size_t)idx3[r * 3 + 1] * o, qb + (size_t)idx3[r * 3 + 2] * o, w3[r * 3 + 0], w3[r * 3 + 1],
+                    w3[r * 3 + 2], lin ? lin + r * (long)o : nullptr, skip + r * (long)c1, c1, wb, bias, relu);
     }
 }
 
 // ---- first layer of a feature-propagation module with the interpolation and the concatenation fused into its A operand:
 //   out[r, o] = relu?( sum_k X[r, k] Wt[k, o] + bias[o] ),   r = (scene b, unknown point p),
-//   X[r, 0:c2]      = w0 f[i0, :] + w1 f[i1, :] + w2 f[i2, :]   (three_interpolate, interpolate_gpu.cu:77-97, the same fmaf
-//                     expression as the stand-alone kernels)     f = known_feats (b, m, c2) channels-last
+//   X[r, 0:c2]      = w0 f[i0, :] + w1 f[i1, :] + w2 f[i2, :]   (three_interpolate, the same fmaf expression as the stand-alone
+//                     kernels)                                   f = known_feats (b, m, c2) channels-last
 //   X[r, c2:c2+c1]  = unknown_feats[b, p, :]                     (the skip connection, pointnet2_modules.py:147-150)
 // so neither the interpolated tensor nor the (rows, c2 + c1) concat buffer exists (135 MB per batch at FP1).
-__global__ __launch_bounds__(256) void interp_gemm_kernel(int c2, int c1, int o_dim, int n, int m, const float *__restrict__ known_feats,
+// PRE (ws3d_qinterp_gemm): the A operand is the FIRST layer of the module, built on the fly as ws3d_qinterp_rows builds it --
+//   x[r, k] = relu_a?( w0 Q[i0, k] + w1 Q[i1, k] + w2 Q[i2, k] + (lin[r, k]  |  sum_j skip[r, j] wb[j, k] + b1[k]) )
+// with known_feats = Q (c2 = the layer's width), unknown_feats = the c1 <= 4 skip channels of the second form -- and the
+// product is the SECOND layer: K = c2, no concatenated columns.
+template <int MB, bool PRE>
+struct InterpA {
+    const float *f0[MB], *f1[MB], *f2[MB], *urow[MB], *lrow[MB];
+    float w0[MB], w1[MB], w2[MB];
+    int c2, c1, relu_a;
+    const float *wb, *b1;
+    // r0: the thread's row of the tile (+ 64 i)
+    __device__ __forceinline__ InterpA(long r0, int c2_, int c1_, int n, int m, const float *__restrict__ known_feats, const float *__restrict__ unknown_feats,
+                                       const int32_t *__restrict__ idx3, const float *__restrict__ w3, const float *__restrict__ lin,
+                                       const float *__restrict__ wb_, const float *__restrict__ b1_, int relu_a_)
+        : c2(c2_), c1(c1_), relu_a(relu_a_), wb(wb_), b1(b1_) {
+#pragma unroll
+        for (int i = 0; i < MB; ++i) {
+            const long r = r0 + 64 * i;
+            const float *base = known_feats + (size_t)(r / n) * m * c2;
+            f0[i] = base + (size_t)idx3[r * 3 + 0] * c2; f1[i] = base + (size_t)idx3[r * 3 + 1] * c2; f2[i] = base + (size_t)idx3[r * 3 + 2] * c2;
+            w0[i] = w3[r * 3 + 0]; w1[i] = w3[r * 3 + 1]; w2[i] = w3[r * 3 + 2];
+            urow[i] = unknown_feats ? unknown_feats + (size_t)r * c1 : nullptr;
+            lrow[i] = (PRE && lin) ? lin + (size_t)r * c2 : nullptr;
+        }
+    }
+    __device__ __forceinline__ float4 operator()(int i, int k) const {
+        if (k < c2) {
+            if (PRE) return qrow_f4(k, c2, f0[i], f1[i], f2[i], w0[i], w1[i], w2[i], lrow[i], urow[i], c1, wb, b1, relu_a);
+            return interp3(w0[i], ld4(f0[i] + k), w1[i], ld4(f1[i] + k), w2[i], ld4(f2[i] + k));
+        }
+        if (PRE) return f4_zero();
+        const int ku = k - c2;
+        if (ku + 3 < c1) return ld4(urow[i] + ku);                                    // c1 % 4 == 0: aligned
+        float v[4] = {0.f, 0.f, 0.f, 0.f};                                            // the ragged tail (c1 = 1 at FP1)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) if (ku + q < c1) v[q] = urow[i][ku + q];
+        return make_float4(v[0], v[1], v[2], v[3]);
+    }
+};
+
+// one (64 MB) x (64 NB) output tile, tile number vb of the XCD-aware order
+template <int MB, int NB, bool PRE>
+__device__ __forceinline__ void interp_gemm_tile(long vb, float (&xs)[2][GP_KT][64 * MB + 1], float (&ws)[2][GP_KT][64 * NB], int c2, int c1, int o_dim, int n, int m, const float *__restrict__ known_feats,
+                                                 const float *__restrict__ unknown_feats, const int32_t *__restrict__ idx3, const float *__restrict__ w3,
+                                                 const float *__restrict__ wt, const float *__restrict__ bias, int relu, float *__restrict__ out, int tps,
+                                                 const float *__restrict__ lin, const float *__restrict__ wb, const float *__restrict__ b1, int relu_a) {
+    const Wave w;
+    long row_tile;
+    int col_tile;
+    gg_tile<true>(o_dim / (64 * NB), tps, vb, row_tile, col_tile);
+    const long row0 = row_tile * (64 * MB);
+    const int col0 = col_tile * (64 * NB);
+    const InterpA<MB, PRE> load_a(row0 + (w.tid >> 2), c2, c1, n, m, known_feats, unknown_feats, idx3, w3, lin, wb, b1, relu_a);
+    floatx16 acc[MB][NB];
+    mfma_k_loop<MB, NB, false>(w, acc, xs, ws, PRE ? c2 : c2 + c1, load_a, wt, o_dim, col0);
+#pragma unroll
+    for (int i = 0; i < MB; ++i)
+#pragma unroll
+        for (int j = 0; j < NB; ++j) store_rows(w, acc[i][j], bias, relu, out, o_dim, row0 + sub_row<MB>(w, i), col0 + sub_col<NB, false>(w, j) + w.l32);
+}
+
+// the 64 x 64 tile, one per workgroup.  The second launch bound asks for the 8 waves per SIMD that the other 64 x 64 kernels of this
+// file get by themselves (16.5 KB of LDS allow them): without it the register allocator lands two registers above that budget
+__global__ __launch_bounds__(256, 8) void interp_gemm_kernel(int c2, int c1, int o_dim, int n, int m, const float *__restrict__ known_feats,
                                                           const float *__restrict__ unknown_feats, const int32_t *__restrict__ idx3,
                                                           const float *__restrict__ w3, const float *__restrict__ wt,
                                                           const float *__restrict__ bias, int relu, float *__restrict__ out, int tps) {
-    __shared__ float xs[2][GP_KT][GP_XS];     // [k][row]
-    __shared__ float ws[2][GP_KT][64];        // [k][col]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
-    long row_tile;
-    int col_tile;
-    gg_tile(o_dim / 64, tps, row_tile, col_tile);
-    const long row0 = row_tile * 64;
-    const int col0 = col_tile * 64;
-    const int k_dim = c2 + c1;
-    const int xr = tid >> 2, xk = (tid & 3) * 4;
-    const int wk = tid >> 4, wc = (tid & 15) * 4;
-    const long r = row0 + xr;
-    const long b = r / n;
-    const int i0 = idx3[r * 3 + 0], i1 = idx3[r * 3 + 1], i2 = idx3[r * 3 + 2];
-    const float w0 = w3[r * 3 + 0], w1 = w3[r * 3 + 1], w2 = w3[r * 3 + 2];
-    const float *f0 = known_feats + ((size_t)b * m + (size_t)i0) * c2, *f1 = known_feats + ((size_t)b * m + (size_t)i1) * c2,
-                *f2 = known_feats + ((size_t)b * m + (size_t)i2) * c2;
-    const float *urow = unknown_feats ? unknown_feats + (size_t)r * c1 : nullptr;
-    auto load_x = [&](int k0) {
-        const int k = k0 + xk;
-        if (k < c2) {
-            const float4 p0 = *reinterpret_cast<const float4 *>(f0 + k), p1 = *reinterpret_cast<const float4 *>(f1 + k),
-                         p2 = *reinterpret_cast<const float4 *>(f2 + k);
-            return make_float4(__builtin_fmaf(w2, p2.x, __builtin_fmaf(w0, p0.x, w1 * p1.x)), __builtin_fmaf(w2, p2.y, __builtin_fmaf(w0, p0.y, w1 * p1.y)),
-                               __builtin_fmaf(w2, p2.z, __builtin_fmaf(w0, p0.z, w1 * p1.z)), __builtin_fmaf(w2, p2.w, __builtin_fmaf(w0, p0.w, w1 * p1.w)));
-        }
-        const int ku = k - c2;
-        if (ku + 3 < c1) return *reinterpret_cast<const float4 *>(urow + ku);          // c1 % 4 == 0: aligned
-        float v[4] = {0.f, 0.f, 0.f, 0.f};                                            // the ragged tail (c1 = 1 at FP1)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) if (ku + q < c1) v[q] = urow[ku + q];
-        return make_float4(v[0], v[1], v[2], v[3]);
-    };
-    auto load_w = [&](int k0) {
-        const int k = k0 + wk;
-        return k < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)k * o_dim + col0 + wc) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stage = [&](int buf, const float4 xv, const float4 wv) {
-        xs[buf][xk + 0][xr] = xv.x; xs[buf][xk + 1][xr] = xv.y; xs[buf][xk + 2][xr] = xv.z; xs[buf][xk + 3][xr] = xv.w;
-        *reinterpret_cast<float4 *>(&ws[buf][wk][wc]) = wv;
-    };
-    floatx16 acc;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-    float4 xv = load_x(0), wv = load_w(0);
-    stage(0, xv, wv);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 + (lane & 31), bc = wn * 32 + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) { xv = load_x((t + 1) * GP_KT); wv = load_w((t + 1) * GP_KT); }
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[cur][k + kh][ar], ws[cur][k + kh][bc], acc, 0, 0, 0);
-        if (t + 1 < ntiles) stage(cur ^ 1, xv, wv);
-        __syncthreads();
-    }
-    const int col = col0 + bc;
-    const float bv = bias ? bias[col] : 0.f;
-    float *o = out + (row0 + wm * 32 + 4 * (lane >> 5)) * (long)o_dim + col;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        float y = acc[v] + bv;
-        if (relu) y = y < 0.f ? 0.f : y;
-        o[(long)(8 * (v / 4) + (v % 4)) * o_dim] = y;
-    }
+    __shared__ float xs[2][GP_KT][GP_XS];                                       // [k][row]
+    __shared__ __attribute__((aligned(16))) float ws[2][GP_KT][64];             // [k][col]
+    interp_gemm_tile<1, 1, false>(blockIdx.x, xs, ws, c2, c1, o_dim, n, m, known_feats, unknown_feats, idx3, w3, wt, bias, relu, out, tps, nullptr, nullptr,
+                                  nullptr, 0);
 }
 
-// interp_gemm_kernel with a (64 MB) x (64 NB) output tile (see gemm_pool_big_kernel): besides the lighter L2 / LDS traffic the
+// a (64 MB) x (64 NB) output tile (see gemm_pool_big_kernel): besides the lighter L2 / LDS traffic the
 // interpolated A tile -- three gathered rows and three fmaf per element -- is built once per 64 NB output columns instead of
 // once per 64 (at FP1, 128 output channels: exactly once).
 template <int MB, int NB, bool PRE = false>
@@ -1248,147 +557,13 @@ __global__ __launch_bounds__(256) void interp_gemm_big_kernel(int c2, int c1, in
                                                               const float *__restrict__ bias, int relu, float *__restrict__ out, int tps,
                                                               const float *__restrict__ lin = nullptr, const float *__restrict__ wb = nullptr,
                                                               const float *__restrict__ b1 = nullptr, int relu_a = 0, long total_tiles = 0) {
-    // PRE (ws3d_qinterp_gemm): the A operand is the FIRST layer of the module, built on the fly as ws3d_qinterp_rows builds it --
-    //   x[r, k] = relu_a?( w0 Q[i0, k] + w1 Q[i1, k] + w2 Q[i2, k] + (lin[r, k]  |  sum_j skip[r, j] wb[j, k] + b1[k]) )
-    // with known_feats = Q (c2 = the layer's width), unknown_feats = the c1 <= 4 skip channels of the second form -- and this kernel's
-    // product is the SECOND layer: K = c2, no concatenated columns.
-    constexpr int TM = 64 * MB, TN = 64 * NB, XS = TM + 1;
-    __shared__ float xs[2][GP_KT][XS];        // [k][row]
-    __shared__ float ws[2][GP_KT][TN];        // [k][col]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int wm = w & 1, wn = w >> 1;
+    __shared__ float xs[2][GP_KT][64 * MB + 1];                                 // [k][row]
+    __shared__ __attribute__((aligned(16))) float ws[2][GP_KT][64 * NB];       // [k][col]
     // round 6: a workgroup walks tiles vb = blockIdx.x, + gridDim.x, .. (total_tiles = 0: one tile per workgroup, the launch of rounds
     // 2-5); gridDim.x is a multiple of 8 then, so a workgroup's tiles stay on its XCD's scenes (gg_tile)
     const long n_tiles = total_tiles > 0 ? total_tiles : (long)gridDim.x;
-    for (long vb = blockIdx.x; vb < n_tiles; vb += gridDim.x) {
-    long row_tile;
-    int col_tile;
-    gg_tile(o_dim / TN, tps, row_tile, col_tile, vb);
-    const long row0 = row_tile * TM;
-    const int col0 = col_tile * TN;
-    const int k_dim = PRE ? c2 : c2 + c1;
-    const int xk = (tid & 3) * 4;
-    const float *f0[MB], *f1[MB], *f2[MB], *urow[MB];
-    const float *lrow[MB];
-    float w0[MB], w1[MB], w2[MB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i) {
-        const long r = row0 + (tid >> 2) + 64 * i;
-        const long b = r / n;
-        const float *base = known_feats + (size_t)b * m * c2;
-        f0[i] = base + (size_t)idx3[r * 3 + 0] * c2; f1[i] = base + (size_t)idx3[r * 3 + 1] * c2; f2[i] = base + (size_t)idx3[r * 3 + 2] * c2;
-        w0[i] = w3[r * 3 + 0]; w1[i] = w3[r * 3 + 1]; w2[i] = w3[r * 3 + 2];
-        urow[i] = unknown_feats ? unknown_feats + (size_t)r * c1 : nullptr;
-        lrow[i] = (PRE && lin) ? lin + (size_t)r * c2 : nullptr;
-    }
-    float4 xv[MB], wv[NB];
-    auto load = [&](int k0) {
-        const int k = k0 + xk;
-#pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            if (k < c2) {
-                const float4 p0 = *reinterpret_cast<const float4 *>(f0[i] + k), p1 = *reinterpret_cast<const float4 *>(f1[i] + k),
-                             p2 = *reinterpret_cast<const float4 *>(f2[i] + k);
-                xv[i] = make_float4(__builtin_fmaf(w2[i], p2.x, __builtin_fmaf(w0[i], p0.x, w1[i] * p1.x)),
-                                    __builtin_fmaf(w2[i], p2.y, __builtin_fmaf(w0[i], p0.y, w1[i] * p1.y)),
-                                    __builtin_fmaf(w2[i], p2.z, __builtin_fmaf(w0[i], p0.z, w1[i] * p1.z)),
-                                    __builtin_fmaf(w2[i], p2.w, __builtin_fmaf(w0[i], p0.w, w1[i] * p1.w)));
-                if (PRE) {
-                    float4 y = xv[i];
-                    if (lrow[i]) {
-                        const float4 l4 = *reinterpret_cast<const float4 *>(lrow[i] + k);
-                        y.x += l4.x; y.y += l4.y; y.z += l4.z; y.w += l4.w;
-                    } else {
-                        for (int j = 0; j < c1; ++j) {
-                            const float sv = urow[i][j];
-                            const float4 wv4 = *reinterpret_cast<const float4 *>(wb + (long)j * c2 + k);
-                            y.x = __builtin_fmaf(sv, wv4.x, y.x); y.y = __builtin_fmaf(sv, wv4.y, y.y); y.z = __builtin_fmaf(sv, wv4.z, y.z); y.w = __builtin_fmaf(sv, wv4.w, y.w);
-                        }
-                        if (b1) {
-                            const float4 bv = *reinterpret_cast<const float4 *>(b1 + k);
-                            y.x += bv.x; y.y += bv.y; y.z += bv.z; y.w += bv.w;
-                        }
-                    }
-                    if (relu_a) { y.x = y.x < 0.f ? 0.f : y.x; y.y = y.y < 0.f ? 0.f : y.y; y.z = y.z < 0.f ? 0.f : y.z; y.w = y.w < 0.f ? 0.f : y.w; }
-                    xv[i] = y;
-                }
-            } else if (PRE) {
-                xv[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            } else {
-                const int ku = k - c2;
-                if (ku + 3 < c1) {
-                    xv[i] = *reinterpret_cast<const float4 *>(urow[i] + ku);            // c1 % 4 == 0: aligned
-                } else {
-                    float v[4] = {0.f, 0.f, 0.f, 0.f};                                  // the ragged tail (c1 = 1 at FP1)
-#pragma unroll
-                    for (int q = 0; q < 4; ++q) if (ku + q < c1) v[q] = urow[i][ku + q];
-                    xv[i] = make_float4(v[0], v[1], v[2], v[3]);
-                }
-            }
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int idx = tid + 256 * j, kk = k0 + idx / (16 * NB), c = (idx % (16 * NB)) * 4;
-            wv[j] = kk < k_dim ? *reinterpret_cast<const float4 *>(wt + (long)kk * o_dim + col0 + c) : make_float4(0.f, 0.f, 0.f, 0.f);
-        }
-    };
-    auto stage = [&](int buf) {
-#pragma unroll
-        for (int i = 0; i < MB; ++i) {
-            const int r = (tid >> 2) + 64 * i;
-            xs[buf][xk + 0][r] = xv[i].x; xs[buf][xk + 1][r] = xv[i].y; xs[buf][xk + 2][r] = xv[i].z; xs[buf][xk + 3][r] = xv[i].w;
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int idx = tid + 256 * j;
-            *reinterpret_cast<float4 *>(&ws[buf][idx / (16 * NB)][(idx % (16 * NB)) * 4]) = wv[j];
-        }
-    };
-    floatx16 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int v = 0; v < 16; ++v) acc[i][j][v] = 0.f;
-    load(0);
-    stage(0);
-    __syncthreads();
-    const int ntiles = (k_dim + GP_KT - 1) / GP_KT;
-    const int ar = wm * 32 * MB + (lane & 31), bc = wn * 32 * NB + (lane & 31), kh = lane >> 5;
-    for (int t = 0; t < ntiles; ++t) {
-        const int cur = t & 1;
-        if (t + 1 < ntiles) load((t + 1) * GP_KT);
-#pragma unroll
-        for (int k = 0; k < GP_KT; k += 2) {
-            float a[MB], bq[NB];
-#pragma unroll
-            for (int i = 0; i < MB; ++i) a[i] = xs[cur][k + kh][ar + 32 * i];
-#pragma unroll
-            for (int j = 0; j < NB; ++j) bq[j] = ws[cur][k + kh][bc + 32 * j];
-#pragma unroll
-            for (int i = 0; i < MB; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], bq[j], acc[i][j], 0, 0, 0);
-        }
-        if (t + 1 < ntiles) stage(cur ^ 1);
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int col = col0 + bc + 32 * j;
-            const float bv = bias ? bias[col] : 0.f;
-            float *o = out + (row0 + wm * 32 * MB + 32 * i + 4 * (lane >> 5)) * (long)o_dim + col;
-#pragma unroll
-            for (int v = 0; v < 16; ++v) {
-                float y = acc[i][j][v] + bv;
-                if (relu) y = y < 0.f ? 0.f : y;
-                o[(long)(8 * (v / 4) + (v % 4)) * o_dim] = y;
-            }
-        }
-    }
+    for (long vb = blockIdx.x; vb < n_tiles; vb += gridDim.x)
+        interp_gemm_tile<MB, NB, PRE>(vb, xs, ws, c2, c1, o_dim, n, m, known_feats, unknown_feats, idx3, w3, wt, bias, relu, out, tps, lin, wb, b1, relu_a);
 }
 
 }  // namespace ws3d
@@ -1404,36 +579,16 @@ extern "C" int ws3d_gemm_pool(long rows, int nsample, int k_dim, int o_dim, cons
         return WS3D_E_UNSUPPORTED;
     }
     if (rows == 0) return WS3D_OK;
-    constexpr int xcd_env = 1;        // XCD-aware tile order (the plain order was an A/B switch until round 4)
     // tile: 128 x 128 when that still gives two workgroups per CU (same kernel time as 64 x 64 -- the matrix pipe is the bound at
     // either size -- at half the L2 and LDS traffic: +1.3 % in the 20-deep pipeline), else 64 x 64 (128 x 64 and 64 x 128 were
     // measured too: profiles/r02_gemm_pool_tiles.txt)
-    const int tile_env = (rows % 128 == 0 && o_dim % 128 == 0 && (rows / 128) * (o_dim / 128) >= 512) ? 22 : 11;
-    {
-        const int mb = tile_env / 10, nb = tile_env % 10;
-        if (tile_env != 11) {
-            const long rt = rows / (64 * mb);
-            const int xc = (xcd_env && rt % 8 == 0) ? 1 : 0;
-            const dim3 grid((unsigned)((o_dim / (64 * nb)) * rt)), block(256);
-#define GP_BIG(M_, N_)                                                                                                              \
-    if (mb == M_ && nb == N_) {                                                                                                     \
-        if (nsample == 16)                                                                                                          \
-            hipLaunchKernelGGL((gemm_pool_big_kernel<16, M_, N_>), grid, block, 0, as_stream(stream), k_dim, o_dim, x_rows, wt, bias, relu, out, out_stride, xc, gate, gate_limit); \
-        else                                                                                                                        \
-            hipLaunchKernelGGL((gemm_pool_big_kernel<32, M_, N_>), grid, block, 0, as_stream(stream), k_dim, o_dim, x_rows, wt, bias, relu, out, out_stride, xc, gate, gate_limit); \
-        return check_launch("ws3d_gemm_pool");                                                                                      \
-    }
-            GP_BIG(2, 2)
-#undef GP_BIG
-        }
-    }
-    const long row_tiles = rows / 64;
-    const int xcd = (xcd_env && row_tiles % 8 == 0) ? 1 : 0;
-    const dim3 grid((unsigned)((o_dim / 64) * row_tiles)), block(256);
-    if (nsample == 16)
-        hipLaunchKernelGGL(gemm_pool_kernel<16>, grid, block, 0, as_stream(stream), k_dim, o_dim, x_rows, wt, bias, relu, out, out_stride, xcd, gate, gate_limit);
-    else
-        hipLaunchKernelGGL(gemm_pool_kernel<32>, grid, block, 0, as_stream(stream), k_dim, o_dim, x_rows, wt, bias, relu, out, out_stride, xcd, gate, gate_limit);
+    const int mb = (rows % 128 == 0 && o_dim % 128 == 0 && (rows / 128) * (o_dim / 128) >= 512) ? 2 : 1;      // (MB, NB) = (mb, mb)
+    const long row_tiles = rows / (64 * mb);
+    const int xcd = row_tiles % 8 == 0 ? 1 : 0;       // XCD-aware tile order (the plain order was an A/B switch until round 4)
+    const dim3 grid((unsigned)((o_dim / (64 * mb)) * row_tiles)), block(256);
+    const auto kern = mb == 2 ? (nsample == 16 ? gemm_pool_big_kernel<16, 2, 2> : gemm_pool_big_kernel<32, 2, 2>)
+                              : (nsample == 16 ? gemm_pool_big_kernel<16, 1, 1> : gemm_pool_big_kernel<32, 1, 1>);
+    hipLaunchKernelGGL(kern, grid, block, 0, as_stream(stream), k_dim, o_dim, x_rows, wt, bias, relu, out, out_stride, xcd, gate, gate_limit);
     return check_launch("ws3d_gemm_pool");
 }
 
@@ -1471,24 +626,15 @@ extern "C" int ws3d_interp_gemm(int b, int n, int m, int c2, int c1, int o_dim, 
     }
     if (rows == 0) return WS3D_OK;
     constexpr int xcd_env = 1;
+    const int tps = (xcd_env && (b & 7) == 0 && n % 64 == 0) ? n / 64 : 0;      // both tiles are 64 rows high
     // 64 x 128 output tiles where they leave two workgroups per CU (FP1..FP3 of the c3 network): the interpolated A tile is built
     // half as often; measured 120 / 119 / 81 us against 128 / 131 / 82 at 64 x 64 and 119 / 123 / 90 at 128 x 128
     // (profiles/r02_interp_gemm_tiles.txt)
-    const int tile = (o_dim % 128 == 0 && (rows / 64) * (o_dim / 128) >= 512) ? 12 : 11;
-    const int mb = tile / 10, nb = tile % 10;
-    if (tile != 11 && rows % (64 * mb) == 0 && o_dim % (64 * nb) == 0) {
-        const int tpsb = (xcd_env && (b & 7) == 0 && n % (64 * mb) == 0) ? n / (64 * mb) : 0;
-        const dim3 grid((unsigned)((o_dim / (64 * nb)) * (rows / (64 * mb))));
-#define IG_BIG(M_, N_)                                                                                                                  \
-    if (mb == M_ && nb == N_) {                                                                                                         \
-        hipLaunchKernelGGL((interp_gemm_big_kernel<M_, N_>), grid, dim3(256), 0, as_stream(stream), c2, c1, o_dim, n, m, known_feats,   \
-                           unknown_feats, idx, weight, wt, bias, relu, out, tpsb);                                                      \
-        return check_launch("ws3d_interp_gemm");                                                                                        \
+    if (o_dim % 128 == 0 && (rows / 64) * (o_dim / 128) >= 512) {
+        hipLaunchKernelGGL((interp_gemm_big_kernel<1, 2>), dim3((unsigned)((o_dim / 128) * (rows / 64))), dim3(256), 0, as_stream(stream), c2, c1, o_dim, n, m,
+                           known_feats, unknown_feats, idx, weight, wt, bias, relu, out, tps);
+        return check_launch("ws3d_interp_gemm");
     }
-        IG_BIG(1, 2)
-#undef IG_BIG
-    }
-    const int tps = (xcd_env && (b & 7) == 0 && n % 64 == 0) ? n / 64 : 0;
     hipLaunchKernelGGL(interp_gemm_kernel, dim3((unsigned)((o_dim / 64) * (rows / 64))), dim3(256), 0, as_stream(stream), c2, c1, o_dim, n, m,
                        known_feats, unknown_feats, idx, weight, wt, bias, relu, out, tps);
     return check_launch("ws3d_interp_gemm");
