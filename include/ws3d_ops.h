@@ -638,6 +638,39 @@ WS3D_API int ws3d_roipool3d_ws(int batch_size, int pts_num, int boxes_num, int f
 WS3D_API int ws3d_pts_in_boxes3d(int boxes_num, int pts_num, const float *pts, const float *boxes3d,
                         int64_t *flag, ws3d_stream_t stream);
 
+/* ------------------------------------------------- Stage-2 instance clouds (no reference op: Python loops) */
+
+/* The cut between Stage 1 and Stage 2.  In the reference every centre kept by the radius NMS becomes an instance cloud: the scene
+ * points whose (x, z) distance to the centre is below 4.0 m, in scene order, shifted to the centre, with reflectance and a per-point
+ * score channel (generate_box_dataset.py:197-229, 293-307 stores them; tools/eval_auto.py:286-292, 323-372 feeds each to rcnn_forward;
+ * lib/datasets/kitti_boxplace_dataset.py:327-342 brings a stored cloud to 512 rows).  Both drivers use an (N x K) distance matrix and
+ * a Python loop over the centres with boolean-mask indexing; here one launch serves a batch.  Additive to ABI 6.
+ *   pts (B,N,4) x, y, z, reflectance; score (B,N) sigmoid of rpn_cls; feats (B,N,C) channels-last or NULL with C = 0 (C % 4 == 0,
+ *   16-byte aligned); centres (B,K,3) -- the caller chooses the y it is shifted by: 0 reproduces generate_box_dataset.py:226, 1.65
+ *   tools/eval_auto.py:323; num (B) int32 valid centre slots per scene or NULL (all K).
+ *   member: sqrtf(dx*dx + dz*dz) < radius, dx = cx - px, dz = cz - pz, nothing contracted (lib/utils/distance.py:3); NaN = outside.
+ *   row of a member: (px - cx, py - cy, pz - cz, reflectance, m), m = score (mask_mode 0, generate_box_dataset.py:222) or
+ *   (score > mask_thresh ? 1 : 0) - 0.5 (mask_mode 1, tools/eval_auto.py:345, 367); members in ascending point index.
+ * Fixed form: cloud (B,K,S,5), cloud_feats (B,K,S,C) (with features), count (B,K) int32 = the TRUE number of members (not capped at S),
+ * pts_idx (B,K,S) int32 or NULL.  With t = min(count, S): row j < t is the j-th member, row j >= t repeats row j mod t
+ * (kitti_boxplace_dataset.py:327-337).  count == 0 and every slot k >= num[b]: all-zero rows, count 0, pts_idx 0.  EVERY output element
+ * is written (the ws3d_roipool3d_fill convention).  No allocation, no host synchronisation, no atomics; capturable.
+ * B or K == 0: nothing to do; N == 0: the zeros are written.  S * 24 bytes of LDS: S <= 6400.                                        */
+WS3D_API int ws3d_instance_clouds(int batch, int pts_num, int centres_num, int feat_len, int sampled_pts_num, float radius, int mask_mode,
+                                  float mask_thresh, const float *pts, const float *score, const float *feats, const float *centres,
+                                  const int32_t *num, float *cloud, float *cloud_feats, int32_t *count, int32_t *pts_idx,
+                                  ws3d_stream_t stream);
+/* Ragged form, what generate_box_dataset.py:220-229 stores and tools/eval_auto.py:341-372 feeds.  ws3d_instance_clouds_count writes
+ * count (B,K) int32 (0 for slots k >= num[b]); the caller forms offsets (B*K + 1) int64, the exclusive prefix sum in (b, k) order, and
+ * allocates; ws3d_instance_clouds_emit writes rows (total,5), row_feats (total,C) (with features) and row_idx (total) int32 or NULL:
+ * centre (b, k)'s members at offsets[b*K + k] ... in ascending point index.  A row that would fall at or past offsets[b*K + k + 1]
+ * is dropped, so offsets that no longer match the inputs cannot make the launch write outside a centre's range.                      */
+WS3D_API int ws3d_instance_clouds_count(int batch, int pts_num, int centres_num, float radius, const float *pts, const float *centres,
+                                        const int32_t *num, int32_t *count, ws3d_stream_t stream);
+WS3D_API int ws3d_instance_clouds_emit(int batch, int pts_num, int centres_num, int feat_len, float radius, int mask_mode, float mask_thresh,
+                                       const float *pts, const float *score, const float *feats, const float *centres, const int32_t *num,
+                                       const int64_t *offsets, float *rows, float *row_feats, int32_t *row_idx, ws3d_stream_t stream);
+
 /* ------------------------------------------------- KITTI evaluation (kitti_object_eval_python) */
 
 /* Frames are CSR ranges: gt_off / dt_off (frames + 1) int32 offsets of each frame's ground truths / detections, out_off (frames + 1)

@@ -128,6 +128,9 @@ SIGNATURES = {
     "ws3d_roipool3d_workspace_bytes": (C.c_size_t, [_i, _i]),
     "ws3d_roipool3d_ws": (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, C.c_size_t, _vp]),
     "ws3d_pts_in_boxes3d": (_i, [_i, _i, _vp, _vp, _vp, _vp]),
+    "ws3d_instance_clouds": (_i, [_i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws3d_instance_clouds_count": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
+    "ws3d_instance_clouds_emit": (_i, [_i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_kitti_overlaps": (_i, [_i, _i, _i, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_kitti_collect_scores": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "ws3d_kitti_count_workspace_bytes": (_sz, [_i, _i]),

@@ -1385,6 +1385,93 @@ def pts_in_boxes3d_device(pts, boxes3d):
     return flag
 
 
+# ------------------------------------------------------------------ Stage-2 instance clouds (csrc/instance_clouds.hip)
+def _instance_sizes(pts, score, feats, centres, num):
+    _f32(pts, "pts"); _f32(score, "score"); _f32(centres, "centres")
+    B, N = pts.size(0), pts.size(1)
+    if pts.dim() != 3 or pts.size(2) != 4 or tuple(score.shape) != (B, N) or centres.dim() != 3 or centres.size(0) != B or centres.size(2) != 3:
+        raise Ws3dError(f"instance_clouds: pts (B,N,4), score (B,N), centres (B,K,3) expected, got {tuple(pts.shape)} {tuple(score.shape)} {tuple(centres.shape)}")
+    C = 0
+    if feats is not None:
+        _f32(feats, "feats")
+        if feats.dim() != 3 or tuple(feats.shape[:2]) != (B, N):
+            raise Ws3dError(f"instance_clouds: feats (B,N,C) expected, got {tuple(feats.shape)}")
+        C = feats.size(2)
+    if num is not None:
+        _i32(num, "num")
+        if tuple(num.shape) != (B,):
+            raise Ws3dError(f"instance_clouds: num (B) expected, got {tuple(num.shape)}")
+    return B, N, centres.size(1), C
+
+
+def instance_clouds_forward(pts, score, feats, centres, num, radius, mask_mode, mask_thresh, cloud, cloud_feats, count, pts_idx=None):
+    """ws3d_instance_clouds: the fixed form (B,K,S,5) (+ (B,K,S,C)); every output element is written.  generate_box_dataset.py:197-229,
+    tools/eval_auto.py:323-372, kitti_boxplace_dataset.py:327-337.  ws3d extension."""
+    dev = _dev(pts, score, feats, centres, num, cloud, cloud_feats, count, pts_idx)
+    B, N, K, C = _instance_sizes(pts, score, feats, centres, num)
+    _f32(cloud, "cloud"); _i32(count, "count")
+    S = cloud.size(2)
+    if tuple(cloud.shape) != (B, K, S, 5) or tuple(count.shape) != (B, K):
+        raise Ws3dError(f"instance_clouds: cloud (B,K,S,5) / count (B,K) expected, got {tuple(cloud.shape)} {tuple(count.shape)}")
+    if C:
+        if cloud_feats is None:
+            raise Ws3dError("instance_clouds: feats given without cloud_feats")
+        _f32(cloud_feats, "cloud_feats")
+        if tuple(cloud_feats.shape) != (B, K, S, C):
+            raise Ws3dError(f"instance_clouds: cloud_feats (B,K,S,C) expected, got {tuple(cloud_feats.shape)}")
+    if pts_idx is not None:
+        _i32(pts_idx, "pts_idx")
+        if tuple(pts_idx.shape) != (B, K, S):
+            raise Ws3dError(f"instance_clouds: pts_idx (B,K,S) expected, got {tuple(pts_idx.shape)}")
+    with _on(dev):
+        check(_lib.load().ws3d_instance_clouds(B, N, K, C, S, float(radius), int(mask_mode), float(mask_thresh), _p(pts), _p(score), _p(feats),
+                                               _p(centres), _p(num), _p(cloud), _p(cloud_feats if C else None), _p(count), _p(pts_idx),
+                                               _stream()), "instance_clouds")
+    return 1
+
+
+def instance_clouds_count(pts, centres, num, radius, count):
+    """ws3d_instance_clouds_count: count (B,K) int32 members per centre"""
+    dev = _dev(pts, centres, num, count)
+    _f32(pts, "pts"); _f32(centres, "centres"); _i32(count, "count")
+    if num is not None:
+        _i32(num, "num")
+    B, N, K = pts.size(0), pts.size(1), centres.size(1)
+    if pts.dim() != 3 or pts.size(2) != 4 or tuple(centres.shape) != (B, K, 3) or tuple(count.shape) != (B, K) or (num is not None and tuple(num.shape) != (B,)):
+        raise Ws3dError("instance_clouds_count: pts (B,N,4), centres (B,K,3), num (B), count (B,K) expected")
+    with _on(dev):
+        check(_lib.load().ws3d_instance_clouds_count(B, N, K, float(radius), _p(pts), _p(centres), _p(num), _p(count), _stream()),
+              "instance_clouds_count")
+    return 1
+
+
+def instance_clouds_emit(pts, score, feats, centres, num, radius, mask_mode, mask_thresh, offsets, rows, row_feats, row_idx=None):
+    """ws3d_instance_clouds_emit: offsets (B*K+1) int64 -> rows (total,5) (+ row_feats (total,C), row_idx (total))"""
+    dev = _dev(pts, score, feats, centres, num, offsets, rows, row_feats, row_idx)
+    B, N, K, C = _instance_sizes(pts, score, feats, centres, num)
+    _f32(rows, "rows")
+    if offsets.dtype != torch.int64 or tuple(offsets.shape) != (B * K + 1,):
+        raise Ws3dError(f"instance_clouds_emit: offsets (B*K+1) int64 expected, got {tuple(offsets.shape)} {offsets.dtype}")
+    total = rows.size(0)
+    if tuple(rows.shape) != (total, 5):
+        raise Ws3dError(f"instance_clouds_emit: rows (total,5) expected, got {tuple(rows.shape)}")
+    if C:
+        if row_feats is None:
+            raise Ws3dError("instance_clouds_emit: feats given without row_feats")
+        _f32(row_feats, "row_feats")
+        if tuple(row_feats.shape) != (total, C):
+            raise Ws3dError(f"instance_clouds_emit: row_feats (total,C) expected, got {tuple(row_feats.shape)}")
+    if row_idx is not None:
+        _i32(row_idx, "row_idx")
+        if tuple(row_idx.shape) != (total,):
+            raise Ws3dError(f"instance_clouds_emit: row_idx (total) expected, got {tuple(row_idx.shape)}")
+    with _on(dev):
+        check(_lib.load().ws3d_instance_clouds_emit(B, N, K, C, float(radius), int(mask_mode), float(mask_thresh), _p(pts), _p(score), _p(feats),
+                                                    _p(centres), _p(num), _p(offsets), _p(rows), _p(row_feats if C else None), _p(row_idx),
+                                                    _stream()), "instance_clouds_emit")
+    return 1
+
+
 def _default_device():
     if not torch.cuda.is_available():
         raise Ws3dError("no HIP device: the reference's *_cpu entry points are served by the MI355X "

@@ -2,9 +2,11 @@
 
     python -m ws3d_amd.infer_kitti --root /data/KITTI/object --split val --out results/ [--ckpt x.pth]
 
-The counterpart of the reference's ``tools/eval_auto.py`` / ``generate_box_dataset.py`` drivers
-for the part of the pipeline this repository implements: ingest
-(``ws3d_amd.kitti_io``) -> Stage-1 forward -> on-device proposal stage -> ``save_kitti_format``.
+The counterpart of the Stage-1 half of the reference's ``tools/eval_auto.py`` driver:
+ingest (``ws3d_amd.kitti_io``) -> Stage-1 forward -> on-device proposal stage -> ``save_kitti_format``.
+The Stage-2 training set that ``generate_box_dataset.py`` writes (the instance clouds around the kept
+centres) is produced by ``ws3d_amd.gen_box_dataset``; the Stage-2 inputs ``eval_auto.py`` cuts at
+inference time by ``stage1.stage2_inputs``.
 Weights come from a reference checkpoint (``model_state``, identical keys) or, without one, from
 the seeded initialisation used by the benchmarks.
 """

@@ -304,3 +304,66 @@ def stage1_inference(model: Stage1Net, pts_input: torch.Tensor, cfg: RPNConfig =
     pooled, empty = roipool3d_ops.roipool3d_gpu(out['backbone_xyz'], feats, boxes, cfg.roi_extra_width,
                                                 sampled_pt_num=cfg.roi_sampled_pts, enlarged=enlarged)
     return {'boxes': boxes, 'scores': scores, 'count': count, 'pooled': pooled, 'empty': empty, 'rpn': out}
+
+
+@torch.no_grad()
+def kept_centres(out: dict, cfg: RPNConfig = DEFAULT_CFG, y: float = 0.0, prop_dist: float = 0.3, min_reg_dist: float = 0.2):
+    """``center_proposals`` scene by scene over a batch's rpn_forward dict, padded to fixed shapes: center (B,K,3) with the y
+    column set to ``y`` (decode_center_target leaves it 0), center_score (B,K) sigmoid scores, num (B) int32 kept centres per
+    scene; K = the largest number kept, at least 1; padding slots are zero."""
+    B = out['backbone_xyz'].shape[0]
+    dev = out['backbone_xyz'].device
+    per_scene = []
+    for b in range(B):
+        one = {'backbone_xyz': out['backbone_xyz'][b], 'rpn_cls': out['rpn_cls'][b], 'rpn_reg': out['rpn_reg'][b]}
+        rois, norm, _ = center_proposals(one, cfg, prop_dist, min_reg_dist)
+        per_scene.append((rois, norm))
+    K = max(1, max(r.shape[0] for r, _ in per_scene))
+    center = torch.zeros((B, K, 3), dtype=torch.float32, device=dev)
+    center_score = torch.zeros((B, K), dtype=torch.float32, device=dev)
+    for b, (rois, norm) in enumerate(per_scene):
+        center[b, :rois.shape[0]] = rois
+        center_score[b, :rois.shape[0]] = norm
+    center[:, :, 1] = y
+    num = torch.tensor([r.shape[0] for r, _ in per_scene], dtype=torch.int32, device=dev)
+    return center, center_score, num
+
+
+@torch.no_grad()
+def stage2_inputs(out: dict, pts_input: torch.Tensor, cfg: RPNConfig = DEFAULT_CFG, radius: float = 4.0, sampled_pt_num=512,
+                  ground_y: float = 1.65, with_features: bool = False, prop_dist: float = 0.3, min_reg_dist: float = 0.2):
+    """WS3D's hand-off from Stage 1 to Stage 2 (tools/eval_auto.py:286-292, 323-372) for a batch: every centre that
+    ``center_proposals`` keeps becomes the cloud of scene points within ``radius`` of it in (x, z), in scene order, x and z
+    shifted to the centre and y lowered by ``ground_y`` (eval_auto.py:323), with reflectance and (score > 0.5) - 0.5.
+    out: ``Stage1Net.rpn_forward``'s dict for pts_input (B,N,4).  The centres of a scene come from the existing per-scene
+    ``center_proposals``; they are padded to (B,K,3), K = the largest number kept (at least 1), and cut in ONE launch
+    (``instance_ops``).  Returns a dict under the names rcnn_forward reads (eval_auto.py:369-372):
+      sampled_pt_num = S : cur_box_point (B,K,S,3), cur_box_reflect (B,K,S,1), train_mask (B,K,S,1) [, cur_pts_feature (B,K,S,C)]:
+                           the first S points repeated cyclically (kitti_boxplace_dataset.py:327-337), zero rows for the padding
+                           slots k >= num[b] and for empty cylinders;
+      sampled_pt_num = None : cur_box_point (total,3), cur_box_reflect (total,1), train_mask (total,1) [, cur_pts_feature
+                           (total,C)] and offsets (B*K+1): centre (b, k) owns rows offsets[b*K+k] : offsets[b*K+k+1];
+    plus center (B,K,3) with y = ground_y, center_score (B,K) sigmoid scores, num (B) int32 kept centres per scene, count (B,K)
+    int32 points per cylinder (not capped)."""
+    from . import instance_ops
+    B, N = pts_input.shape[0], pts_input.shape[1]
+    center, center_score, num = kept_centres(out, cfg, ground_y, prop_dist, min_reg_dist)
+    scores = torch.sigmoid(out['rpn_cls'].reshape(B, N))
+    feats = None
+    if with_features:
+        feats = out.get('backbone_features_nlc')
+        if feats is None:
+            feats = out['backbone_features'].transpose(1, 2)
+        feats = feats.contiguous()
+    res = {'center': center, 'center_score': center_score, 'num': num}
+    if sampled_pt_num is None:
+        rows, row_feats, offsets, count = instance_ops.instance_clouds_ragged(pts_input, scores, center, num, radius, mask_mode=1,
+                                                                              mask_thresh=0.5, features=feats)
+        res['offsets'] = offsets
+    else:
+        rows, row_feats, count = instance_ops.instance_clouds(pts_input, scores, center, num, radius, sampled_pt_num, mask_mode=1,
+                                                              mask_thresh=0.5, features=feats)
+    res.update({'cur_box_point': rows[..., 0:3], 'cur_box_reflect': rows[..., 3:4], 'train_mask': rows[..., 4:5], 'count': count})
+    if with_features:
+        res['cur_pts_feature'] = row_feats
+    return res
