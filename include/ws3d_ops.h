@@ -481,6 +481,18 @@ WS3D_API int ws3d_rpn_heads_pack(int o2, const float *w1t, const float *b1, int 
 WS3D_API int ws3d_rpn_heads(long rows, const float *x_rows, int heads, const void *blob_cls, float *out_cls, int *ticket_cls, int o2_reg,
                    const void *blob_reg, float *out_reg, int *ticket_reg, int workgroups, ws3d_stream_t stream);
 
+/* A plain row GEMM on the bf16 matrix cores at fp32 accuracy (split product: DESIGN.md section 4 item 8; csrc/gemm_rows.hip):
+ *   out (rows, n_dim) = relu?( a (rows, k_dim) @ wt (k_dim, n_dim) + bias ),   a, wt, out fp32 row-major and contiguous, bias may be NULL.
+ * wt is split ONCE per weight set by ws3d_gemm_rows_pack into a device image of ws3d_gemm_rows_pack_bytes(k_dim, n_dim) bytes (16-byte
+ * aligned; 0 = shape not covered): three bf16 planes in the order the kernel's operand reads take them.  a is split inside the kernel.
+ * No split-K and no atomics: every output element is summed by one wave in ascending k, so the launch geometry changes no bit.
+ * Cover: rows % 64 == 0, k_dim % 32 == 0, n_dim % 64 == 0 (both <= 4096), a / pack / out / bias 16-byte aligned; anything else returns
+ * WS3D_E_UNSUPPORTED with nothing launched (the caller runs the library GEMM).  ws3d extension, used by ws3d_amd/fastpath.py.        */
+WS3D_API size_t ws3d_gemm_rows_pack_bytes(int k_dim, int n_dim);
+WS3D_API int ws3d_gemm_rows_pack(int k_dim, int n_dim, const float *wt, void *pack, ws3d_stream_t stream);
+WS3D_API int ws3d_gemm_rows_split(long rows, int k_dim, int n_dim, const float *a, const void *pack, const float *bias, int relu, float *out,
+                         ws3d_stream_t stream);
+
 /* Both layers of a two-layer feature-propagation module in one kernel (round 4): the first layer's rows are built in the A operand of the
  * second layer's product exactly as ws3d_qinterp_rows builds them,
  *   x = relu1?( w0 Q[i0] + w1 Q[i1] + w2 Q[i2] + (lin (b*n, c)  |  skip (b*n, c1 <= 4) @ wb (c1, c) + b1) ),   out (b*n, o) = relu2?( x @ w2t (c, o) + b2 )

@@ -79,6 +79,9 @@ SIGNATURES = {
     "ws3d_rpn_heads_blob_bytes": (_sz, [_i]),
     "ws3d_rpn_heads_pack": (_i, [_i, _vp, _vp, _i, _vp, _vp, _i, _vp, _vp]),
     "ws3d_rpn_heads": (_i, [C.c_long, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp]),
+    "ws3d_gemm_rows_pack_bytes": (_sz, [_i, _i]),
+    "ws3d_gemm_rows_pack": (_i, [_i, _i, _vp, _vp, _vp]),
+    "ws3d_gemm_rows_split": (_i, [C.c_long, _i, _i, _vp, _vp, _vp, _i, _vp, _vp]),
     "ws3d_decode_center_boxes": (_i, [_i, _i, _i, _f, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ws3d_topk_sorted": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp]),
     "ws3d_topk_workspace_bytes": (C.c_size_t, [_i, _i]),

@@ -942,6 +942,50 @@ def rpn_heads(x2d, heads, blob_cls, blob_reg, o2_reg, tickets, workgroups=0):
     return out_cls, out_reg
 
 
+def gemm_rows_pack(wt):
+    """wt (K,N) fp32 row-major (a folded inference weight, transposed) split into three bf16 planes in the order gemm_rows_split reads
+    them (ws3d_gemm_rows_pack: one small launch) -> a device image, or None when the shape is not covered (K % 32, N % 64).
+    The caller caches it per weight set.  ws3d extension."""
+    dev = _dev(wt)
+    _f32(wt, "wt")
+    if wt.dim() != 2:
+        return None
+    K, N = wt.shape
+    n = int(_lib.load().ws3d_gemm_rows_pack_bytes(K, N))
+    if n == 0:
+        return None
+    pack = torch.empty((n + 15) // 16 * 4, dtype=torch.float32, device=dev)
+    with _on(dev):
+        check(_lib.load().ws3d_gemm_rows_pack(K, N, _p(wt), _p(pack), _stream()), "gemm_rows_pack")
+    return pack
+
+
+def gemm_rows_split(x2d, pack, n_dim, bias=None, relu=False, out=None):
+    """relu?(x2d (R,K) @ W (K,n_dim) + bias) on the bf16 matrix cores at fp32 accuracy (ws3d_gemm_rows_split), W as the image
+    gemm_rows_pack made of it -> (R,n_dim), or None when the shape is not covered (R % 64, K % 32, n_dim % 64, 16-byte aligned
+    contiguous tensors): nothing launched, nothing written, the caller runs the library GEMM.  ws3d extension."""
+    if pack is None or x2d.dim() != 2 or not x2d.is_contiguous() or (bias is not None and (not bias.is_contiguous() or bias.numel() != n_dim)):
+        return None
+    dev = _dev(x2d, pack, bias, out)
+    _f32(x2d, "x2d")
+    R, K = x2d.shape
+    n_dim = int(n_dim)
+    if R % 64 or K % 32 or n_dim % 64 or pack.numel() * pack.element_size() < K * n_dim * 6:
+        return None
+    if bias is not None:
+        _f32(bias, "bias")
+    if out is None:
+        out = torch.empty((R, n_dim), dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != (R, n_dim) or out.dtype != torch.float32:
+        return None
+    with _on(dev):
+        rc = _lib.load().ws3d_gemm_rows_split(R, K, n_dim, _p(x2d), _p(pack), _p(bias), int(bool(relu)), _p(out), _stream())
+    if rc == _lib.E_UNSUPPORTED:
+        return None
+    check(rc, "gemm_rows_split")
+    return out
+
+
 def pool_nsample(x):
     """x (..., nsample) contiguous fp32 -> (max over the last axis (...), position of the maximum u8);
     F.max_pool2d(kernel=[1, nsample]) scan rule (first maximum, NaN propagates).  ws3d extension."""

@@ -102,6 +102,7 @@ MERGED_BINNING = True   # serial order (graph capture): the binned copies of lev
 PER_POINT_FP = True  # FP modules: first layer as (known_feats @ W_a) interpolated + skip @ W_b (ws3d_qinterp_rows)
 FUSED_MLP2_ROWS = True  # ws3d_mlp2_rows: the two layers of a head in one kernel
 FUSED_HEADS = True  # ws3d_rpn_heads: both heads in ONE launch on the bf16 matrix cores at fp32 accuracy (split product); False: the two ws3d_mlp2_rows launches
+SPLIT_GEMMS = True  # ws3d_gemm_rows_split: the backbone's library GEMMs (per-point first layers, the FP modules' known-point / skip products and second layers) on the bf16 matrix cores at fp32 accuracy (split product), shape by shape where _split_gemm_wins; False: torch.mm / addmm / _addmm_activation (hipBLASLt) and their bits
 FUSED_GATHER_GEMM2 = True  # ws3d_gather_gemm2: layers 1 + 2 of SA2-SA4 in one kernel
 BIN_INPUT_AHEAD = True     # eager pass with geometry ahead: bin the input cloud on the search stream beside the first level's sampling kernel
 FUSED_QINTERP_GEMM_MIN_ROWS = 30000    # ws3d_qinterp_gemm (both layers of an FP module in one kernel) from this many rows on (batch 8: FP1, FP2; smaller modules lose, profiles/r04_qinterp_gemm_ab.txt); 1 << 60: never
@@ -151,8 +152,45 @@ def _split_rows(block, wt: torch.Tensor, c2: int):
     return cache[2], cache[3]
 
 
+# Products that stay on the library: (rows, K, N) where ws3d_gemm_rows_split did not win back to back at batch 8
+# (profiles/gemm_rows_vs_library.txt: FP3's known-point product, 32 tiles with a serial K loop of 1024, 27.0 against 19.0 us; the other
+# eleven products win by 15-49 %).  A static rule on the shape: speed only, both forms are fp32-accurate.
+_SPLIT_GEMM_LIBRARY_WINS = frozenset({(512, 1024, 512)})
+
+
+def _split_gemm_wins(rows: int, k: int, n: int) -> bool:
+    return (rows, k, n) not in _SPLIT_GEMM_LIBRARY_WINS
+
+
+def _split_gemm(x2d: torch.Tensor, holder, key: str, wt: torch.Tensor, bias=None, relu: bool = False):
+    """relu?(x2d @ wt + bias) through ws3d_gemm_rows_split -> (rows, N), or None (switch off, the shape stays on the library or is
+    not covered: nothing launched, the caller issues the library GEMM).  The packed image of wt is cached on `holder` (the block
+    or SA module that owns wt) under `key` and replaced when wt is (a captured graph that reads it keeps its own reference:
+    Stage1Pipeline's slots); it is never first built while a stream is capturing -- such a call takes the library."""
+    if not SPLIT_GEMMS or x2d.dim() != 2 or not _split_gemm_wins(x2d.size(0), wt.size(0), wt.size(1)):
+        return None
+    packs = holder.__dict__.get("_gemm_rows_packs")
+    ent = None if packs is None else packs.get(key)
+    if ent is None or ent[0] is not wt:
+        if torch.cuda.is_current_stream_capturing():
+            return None
+        ent = (wt, _C.gemm_rows_pack(wt))
+        holder.__dict__.setdefault("_gemm_rows_packs", {})[key] = ent
+    if ent[1] is None:
+        return None
+    return _C.gemm_rows_split(x2d, ent[1], wt.size(1), bias, relu)
+
+
+def gemm_rows_packs(model):
+    """every packed weight image the forward passes of `model` launch with (for a holder of a captured graph that reads them)"""
+    return [ent[1] for m in model.modules() for ent in m.__dict__.get("_gemm_rows_packs", {}).values() if ent[1] is not None]
+
+
 def _layer(x2d: torch.Tensor, block) -> torch.Tensor:
     wt, bias, relu = _row_weights(block)
+    y = _split_gemm(x2d, block, "row", wt, bias, relu)
+    if y is not None:
+        return y
     if bias is None:
         y = torch.mm(x2d, wt)
         return torch.relu_(y) if relu else y
@@ -333,7 +371,8 @@ def _per_point_l1(sa, feats: torch.Tensor, nbrs):
         cache = (wts, wcat, offs, w1xs)
         if not torch.cuda.is_current_stream_capturing():
             sa.__dict__["_pp_cache"] = cache
-    return torch.mm(feats.view(B * N, C), cache[1]), cache[2], cache[3]
+    p = _split_gemm(feats.view(B * N, C), sa, "pp", cache[1])
+    return (p if p is not None else torch.mm(feats.view(B * N, C), cache[1])), cache[2], cache[3]
 
 
 def _lists_and_pairs(radius, nsample, xyz, new_xyz, sorted_xyz, zeros=None):
@@ -703,12 +742,15 @@ def fp_forward(fp, unknown: torch.Tensor, known: torch.Tensor, unknown_feats, kn
         wt1, b1, r1 = _row_weights(blocks[0])
         wa, wb = _split_rows(blocks[0], wt1, c2)
         m = known_feats.size(1)
-        q = torch.mm(known_feats.reshape(B * m, c2), wa).view(B, m, -1)
+        q = _split_gemm(known_feats.reshape(B * m, c2), blocks[0], "wa", wa)
+        q = (q if q is not None else torch.mm(known_feats.reshape(B * m, c2), wa)).view(B, m, -1)
         fuse2 = len(blocks) == 2 and B * n >= FUSED_QINTERP_GEMM_MIN_ROWS
         if fuse2:
             wt2, b2, r2 = _row_weights(blocks[1])
         if c1 > 4:
-            lin = torch.mm(unknown_feats.reshape(B * n, c1), wb) if b1 is None else torch.addmm(b1, unknown_feats.reshape(B * n, c1), wb)
+            lin = _split_gemm(unknown_feats.reshape(B * n, c1), blocks[0], "wb", wb, b1)
+            if lin is None:
+                lin = torch.mm(unknown_feats.reshape(B * n, c1), wb) if b1 is None else torch.addmm(b1, unknown_feats.reshape(B * n, c1), wb)
             y = _C.qinterp_gemm(q, idx, weight, wt2, b2, r2, lin=lin, relu=r1) if fuse2 else None
             if y is not None:
                 return y.view(B, n, -1)

@@ -206,6 +206,7 @@ class Stage1Pipeline:
                 slot["out"] = self.body(slot["inp"], slot["exchange"])
             slot["graph"] = graph
             slot["heads_blobs"] = fastpath.heads_blobs(self.model.rpn)       # the packed head weights the graph reads (the blocks' caches may be replaced)
+            slot["gemm_rows_packs"] = fastpath.gemm_rows_packs(self.model.rpn)      # ... and the packed weights of ws3d_gemm_rows_split
         except Exception as exc:      # capture is an optimisation: fall back to eager launches on the slot streams
             self.graph_error = repr(exc)
             slot["graph"] = None
