@@ -721,6 +721,35 @@ WS3D_API int ws3d_kitti_count(int metric, int frames, int max_dt, int num_thresh
                               const double *gt_alpha, const double *dt_bbox, const double *dc_bbox, double min_overlap, int compute_aos,
                               void *workspace, size_t workspace_bytes, double *pr, ws3d_stream_t stream);
 
+/* ------------------------------------------------- Stage-2 box network (lib/net/rcnn_net.py, tools/eval_auto.py) */
+
+/* Additive to ABI 6: no existing entry changed.
+ * The front of a tower of RCNNNet for rows = R * pts_per_cloud points in one launch: replaces rcnn_net.py:253-267 (xyz_up_layer,
+ * feature_up_layer, cat, merge_down_layer) and, with box_ce, rcnn_net.py:337-365 (the IoU-net's canonical transform + the can_* layers).
+ *   pts (rows, 5) = [x, y, z, reflectance, mask]; box_ce (R, 7) = [x, y_centre, z, h, w, l, ry] or NULL;
+ *   wx0 (3, 128), wx1 (128, 128), wf0 (2, 128), wf1 (128, 128), wm (256, 128): the layers' W^T (row = input channel), b* (128);
+ *   xyz_out (rows, 3): with a box, the point minus the centre, turned by -ry about y, divided by (l/2, h/2, w/2), all three set to 0 where the
+ *   largest |coordinate| exceeds `extend` (fp32, the reference's operation order); without one, a copy.  feat (rows, 128), channels last:
+ *   relu(wm^T [relu(wx1^T relu(wx0^T xyz_out + bx0) + bx1) ; relu(wf1^T relu(wf0^T [reflectance, mask] + bf0) + bf1)] + bm).
+ * 128 x 128 and 256 x 128 layers on the fp32 matrix cores, k ascending.  Any rows >= 0; tiles of 64 rows may straddle clouds.          */
+WS3D_API int ws3d_stage2_embed(long rows, int pts_per_cloud, const float *pts, const float *box_ce, float extend, const float *wx0,
+                               const float *bx0, const float *wx1, const float *bx1, const float *wf0, const float *bf0, const float *wf1,
+                               const float *bf1, const float *wm, const float *bm, float *xyz_out, float *feat, ws3d_stream_t stream);
+/* rcnn_reg (rows, 4 * loc_bins + 1 + 2 * head_bins + 3) -> pred_boxes3d (rows, 7) = decode_bbox_target_stage_2 as rcnn_net.py:293-302 calls
+ * it (lib/utils/bbox_transform.py:64-179 with a zero roi, get_xz_fine = get_ry_fine = False, y by offset: x = reg[2 loc_bins] * loc_scope,
+ * z = reg[3 loc_bins] * loc_scope, the FIRST maximal heading bin, sizes reg * (h, w, l) + (h, w, l)) and box_ce (rows, 7) = box2center_box
+ * of it (bbox_transform.py:292-296: y - h / 2).                                                                                          */
+WS3D_API int ws3d_stage2_boxes(int rows, int loc_bins, int head_bins, float loc_scope, float h, float w, float l, const float *rcnn_reg,
+                               float *pred_boxes3d, float *box_ce, ws3d_stream_t stream);
+/* The element-wise part of the detection tail for (batch, slots) clouds: center_box2box + refine_box (rcnn_net.py:387-390,
+ * bbox_transform.py:286-303), ry wrapped into (-pi, pi], x and z shifted by center (batch, slots, 3), y by ground_y (eval_auto.py:397-403);
+ * keep (int32 0 / 1) = sigmoid(rcnn_cls) > cls_thresh && rcnn_iou > iou_thresh && the size window size_window[6] = h_lo, h_hi, w_lo, w_hi,
+ * l_lo, l_hi (HOST pointer; all bounds exclusive, eval_auto.py:426-436) && slot < num[scene]; key = rcnn_iou where kept, -1e30 elsewhere:
+ * the per-scene sort keys of the sweep of eval_auto.py:597-609.  boxes (batch, slots, 7) is written for every slot.                     */
+WS3D_API int ws3d_stage2_select(int batch, int slots, float cls_thresh, float iou_thresh, const float *size_window, float ground_y,
+                                const float *box_ce, const float *rcnn_ref, const float *rcnn_cls, const float *rcnn_iou, const float *center,
+                                const int32_t *num, float *boxes, int32_t *keep, float *key, ws3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -139,6 +139,9 @@ SIGNATURES = {
     "ws3d_kitti_count_workspace_bytes": (_sz, [_i, _i]),
     "ws3d_kitti_count": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _i, _vp,
                               _sz, _vp, _vp]),
+    "ws3d_stage2_embed": (_i, [C.c_long, _i, _vp, _vp, _f] + [_vp] * 10 + [_vp, _vp, _vp]),
+    "ws3d_stage2_boxes": (_i, [_i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
+    "ws3d_stage2_select": (_i, [_i, _i, _f, _f, C.POINTER(_f), _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
 }
 
 

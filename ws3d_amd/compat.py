@@ -1516,6 +1516,74 @@ def instance_clouds_emit(pts, score, feats, centres, num, radius, mask_mode, mas
     return 1
 
 
+# ------------------------------------------------------------------ Stage-2 box network (csrc/stage2.hip)
+def stage2_embed(pts, box_ce, wx0, bx0, wx1, bx1, wf0, bf0, wf1, bf1, wm, bm, extend=1.2):
+    """pts (R,P,5) rows [x, y, z, reflectance, mask], box_ce (R,7) or None, the five layers' W^T (3,128) (128,128) (2,128) (128,128)
+    (256,128) and biases (128,) -> (xyz_out (R,P,3), feat (R*P,128)): the front of a tower of RCNNNet in one launch (ws3d_stage2_embed)"""
+    dev = _dev(pts, box_ce, wx0, bx0, wx1, bx1, wf0, bf0, wf1, bf1, wm, bm)
+    for t, name in ((pts, "pts"), (wx0, "wx0"), (bx0, "bx0"), (wx1, "wx1"), (bx1, "bx1"), (wf0, "wf0"), (bf0, "bf0"), (wf1, "wf1"), (bf1, "bf1"),
+                    (wm, "wm"), (bm, "bm")):
+        _f32(t, name)
+    if pts.dim() != 3 or pts.size(2) != 5:
+        raise ValueError("stage2_embed: pts must be (R,P,5), got %s" % (tuple(pts.shape),))
+    R, P = pts.size(0), pts.size(1)
+    if box_ce is not None:
+        _f32(box_ce, "box_ce")
+        if tuple(box_ce.shape) != (R, 7):
+            raise ValueError("stage2_embed: box_ce must be (%d,7), got %s" % (R, tuple(box_ce.shape)))
+    for t, shape, name in ((wx0, (3, 128), "wx0"), (wx1, (128, 128), "wx1"), (wf0, (2, 128), "wf0"), (wf1, (128, 128), "wf1"), (wm, (256, 128), "wm"),
+                           (bx0, (128,), "bx0"), (bx1, (128,), "bx1"), (bf0, (128,), "bf0"), (bf1, (128,), "bf1"), (bm, (128,), "bm")):
+        if tuple(t.shape) != shape:
+            raise ValueError("stage2_embed: %s must be %s, got %s" % (name, shape, tuple(t.shape)))
+    xyz_out = torch.empty((R, P, 3), dtype=torch.float32, device=dev)
+    feat = torch.empty((R * P, 128), dtype=torch.float32, device=dev)
+    if R * P == 0:
+        return xyz_out, feat
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_embed(R * P, P, _p(pts), _p(box_ce), float(extend), _p(wx0), _p(bx0), _p(wx1), _p(bx1), _p(wf0), _p(bf0),
+                                            _p(wf1), _p(bf1), _p(wm), _p(bm), _p(xyz_out), _p(feat), _stream()), "stage2_embed")
+    return xyz_out, feat
+
+
+def stage2_boxes(rcnn_reg, loc_scope, loc_bin_size, num_head_bin, mean_size):
+    """rcnn_reg (R, 4*bins + 1 + 2*num_head_bin + 3) -> (pred_boxes3d (R,7), box_ce (R,7)) (ws3d_stage2_boxes)"""
+    dev = _dev(rcnn_reg)
+    _f32(rcnn_reg, "rcnn_reg")
+    bins = int(loc_scope / loc_bin_size) * 2
+    if rcnn_reg.dim() != 2 or rcnn_reg.size(1) != 4 * bins + 1 + 2 * num_head_bin + 3:
+        raise ValueError("stage2_boxes: rcnn_reg must be (R,%d), got %s" % (4 * bins + 1 + 2 * num_head_bin + 3, tuple(rcnn_reg.shape)))
+    R = rcnn_reg.size(0)
+    pred = torch.empty((R, 7), dtype=torch.float32, device=dev)
+    ce = torch.empty((R, 7), dtype=torch.float32, device=dev)
+    h, w, l = mean_size
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_boxes(R, bins, int(num_head_bin), float(loc_scope), float(h), float(w), float(l), _p(rcnn_reg), _p(pred), _p(ce),
+                                            _stream()), "stage2_boxes")
+    return pred, ce
+
+
+def stage2_select(box_ce, rcnn_ref, rcnn_cls, rcnn_iou, center, num, cls_thresh, iou_thresh, size_window, ground_y):
+    """box_ce (B,K,7), rcnn_ref (B,K,7), rcnn_cls (B,K), rcnn_iou (B,K), center (B,K,3), num (B,) int32 -> (boxes (B,K,7) in the scene's
+    frame, keep (B,K) int32, key (B,K): rcnn_iou where kept, -1e30 elsewhere) (ws3d_stage2_select)"""
+    import ctypes
+    dev = _dev(box_ce, rcnn_ref, rcnn_cls, rcnn_iou, center, num)
+    for t, name in ((box_ce, "box_ce"), (rcnn_ref, "rcnn_ref"), (rcnn_cls, "rcnn_cls"), (rcnn_iou, "rcnn_iou"), (center, "center")):
+        _f32(t, name)
+    _i32(num, "num")
+    B, K = rcnn_cls.shape
+    if (tuple(box_ce.shape) != (B, K, 7) or tuple(rcnn_ref.shape) != (B, K, 7) or tuple(rcnn_iou.shape) != (B, K) or tuple(center.shape) != (B, K, 3)
+            or tuple(num.shape) != (B,)):
+        raise ValueError("stage2_select: shapes must be (B,K,7) (B,K,7) (B,K) (B,K) (B,K,3) (B,)")
+    boxes = torch.empty((B, K, 7), dtype=torch.float32, device=dev)
+    keep = torch.empty((B, K), dtype=torch.int32, device=dev)
+    key = torch.empty((B, K), dtype=torch.float32, device=dev)
+    win = (ctypes.c_float * 6)(*[float(v) for pair in size_window for v in pair])
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_select(B, K, float(cls_thresh), float(iou_thresh), win, float(ground_y), _p(box_ce), _p(rcnn_ref), _p(rcnn_cls),
+                                             _p(rcnn_iou), _p(center), _p(num), _p(boxes), _p(keep), _p(key), _stream()), "stage2_select")
+    return boxes, keep, key
+
+
 def _default_device():
     if not torch.cuda.is_available():
         raise Ws3dError("no HIP device: the reference's *_cpu entry points are served by the MI355X "

@@ -1,0 +1,107 @@
+"""Two-stage inference over a KITTI directory: ``.bin`` scans in, refined 3-D boxes out as KITTI-format result files.
+
+    python -m ws3d_amd.detect_kitti --root /data/KITTI/object --split val --out results/ [--ckpt stage1.pth] [--rcnn_ckpt stage2.pth] [--eval]
+
+The counterpart of the reference's ``tools/eval_auto.py`` driver, eager, batch by batch:
+ingest (``ws3d_amd.kitti_io``) -> ``Stage1Net.rpn_forward`` -> ``stage1.stage2_inputs(sampled_pt_num=512)`` (the instance clouds
+around the kept centres) -> ``Stage2Net.rcnn_forward`` over the real slots in chunks of ``rcnn_batch`` clouds -> ``stage2.detections``
+-> ``save_kitti_format`` with rcnn_iou as the score.  Weights come from reference checkpoints (``model_state``: ``rpn.*`` keys for
+Stage 1, ``rcnn_net.*`` keys for Stage 2, one file may hold both) or, without one, from the seeded initialisation the benchmarks use.
+``infer_kitti`` remains the Stage-1-only driver.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+
+import numpy as np
+import torch
+
+from . import kitti_io, stage1, stage2
+
+OUT_KEYS = ("rcnn_cls", "rcnn_iou", "rcnn_ref", "box_ce")
+
+
+def load_models(ckpt=None, rcnn_ckpt=None, device="cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG):
+    from .seeded import seeded_state_dict
+    dev = torch.device(device)
+    s1 = stage1.Stage1Net(mode="TEST", cfg=cfg).to(dev).eval()
+    if ckpt:
+        state = torch.load(ckpt, map_location="cpu")
+        state = state.get("model_state", state)
+        s1.load_state_dict({k: v for k, v in state.items() if k.startswith("rpn.")}, strict=True)
+    else:
+        s1.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in s1.state_dict().items()}, 0))
+    s2 = stage2.Stage2Net(mode="TEST", cfg=rcnn_cfg, num_point=cfg.roi_sampled_pts).to(dev).eval()
+    if rcnn_ckpt:
+        s2.load_part_ckpt(torch.load(rcnn_ckpt, map_location="cpu"))
+    else:
+        s2.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in s2.state_dict().items()}, 0))
+    return s1, s2
+
+
+@torch.no_grad()
+def detect_batch(s1, s2, pts: torch.Tensor, cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG,
+                 rcnn_batch: int = 800):
+    """pts (B,N,4) scenes -> (boxes (B,K,7), scores (B,K), count (B,)): K = the largest number of centres Stage 1 keeps in a scene"""
+    out = s1.rpn_forward({"pts_input": pts})
+    inp = stage1.stage2_inputs(out, pts, cfg, sampled_pt_num=cfg.roi_sampled_pts, ground_y=rcnn_cfg.ground_y)
+    center, num = inp["center"], inp["num"]
+    B, K = center.shape[0], center.shape[1]
+    real = (torch.arange(K, device=num.device)[None, :] < num[:, None]).reshape(-1).nonzero().reshape(-1)     # (one synchronisation per batch)
+    widths = {"rcnn_cls": 1, "rcnn_iou": 1, "rcnn_ref": 7, "box_ce": 7}
+    full = {k: torch.zeros((B * K, w), dtype=torch.float32, device=pts.device) for k, w in widths.items()}
+    flat = {k: inp[k].reshape(B * K, *inp[k].shape[2:]) for k in ("cur_box_point", "cur_box_reflect", "train_mask")}
+    for i0 in range(0, real.numel(), rcnn_batch):
+        sel = real[i0:i0 + rcnn_batch]
+        res = s2.rcnn_forward({k: v[sel].contiguous() for k, v in flat.items()})
+        for k in OUT_KEYS:
+            full[k][sel] = res[k].reshape(sel.numel(), -1)
+    return stage2.detections(full, center, num, rcnn_cfg)
+
+
+def run(root: str, split: str, out_dir: str, batch: int = 4, ckpt: str | None = None, rcnn_ckpt: str | None = None, npoints: int = 16384,
+        seed: int = 666, device: str = "cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG,
+        rcnn_batch: int = 800) -> list:
+    """returns the list of result files written (one per scene, possibly empty)"""
+    s1, s2 = load_models(ckpt, rcnn_ckpt, device, cfg, rcnn_cfg)
+    scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=np.random.RandomState(seed))     # eval_auto.py:139 seeds numpy with 666
+    os.makedirs(out_dir, exist_ok=True)
+    written = []
+    for i0 in range(0, len(scenes), batch):
+        items = [scenes[i] for i in range(i0, min(i0 + batch, len(scenes)))]
+        pts = torch.from_numpy(kitti_io.collate_scenes(items)["pts_input"]).to(torch.device(device))
+        boxes, scores, count = (t.cpu().numpy() for t in detect_batch(s1, s2, pts, cfg, rcnn_cfg, rcnn_batch))
+        for j, item in enumerate(items):
+            sid, k = int(item["sample_id"]), int(count[j])
+            written.append(kitti_io.save_kitti_format(sid, scenes.get_calib(sid), boxes[j, :k], out_dir, scores[j, :k],
+                                                      scenes.get_image_shape(sid), "Car"))
+    return written
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--root", required=True)
+    ap.add_argument("--split", default="val")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--ckpt", default=None, help="Stage-1 checkpoint (rpn.* keys)")
+    ap.add_argument("--rcnn_ckpt", default=None, help="Stage-2 checkpoint (rcnn_net.* keys)")
+    ap.add_argument("--batch", type=int, default=4)
+    ap.add_argument("--rcnn_batch", type=int, default=800, help="instance clouds per Stage-2 forward (the reference's Stage-2 batch)")
+    ap.add_argument("--npoints", type=int, default=16384)
+    ap.add_argument("--eval", action="store_true",
+                    help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
+    a = ap.parse_args()
+    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.rcnn_ckpt, a.npoints, rcnn_batch=a.rcnn_batch)
+    print(f"{len(files)} result files in {a.out}")
+    if a.eval:
+        from . import kitti_eval
+        result, ret = kitti_eval.evaluate(os.path.join(a.root, "training", "label_2"), a.out,
+                                          os.path.join(a.root, "ImageSets", a.split + ".txt"), current_class=0)
+        print(result, end="")
+        for k, v in ret.items():
+            print(f"{k}: {v:.4f}")
+
+
+if __name__ == "__main__":
+    main()
