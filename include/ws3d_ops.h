@@ -513,6 +513,14 @@ WS3D_API int ws3d_boxes_overlap_bev(int num_a, const float *boxes_a, int num_b, 
 WS3D_API int ws3d_boxes_iou_bev(int num_a, const float *boxes_a, int num_b, const float *boxes_b,
                        float *ans, ws3d_stream_t stream);
 
+/* Additive to ABI 6.  The DIAGONAL of boxes_iou3d_gpu (lib/utils/iou3d/iou3d_utils.py:21-56) for n pairs boxes_a[i], boxes_b[i], each
+ * (n,7) [x, y_bottom, z, h, w, l, ry]: overlap_bev[i], iou2d[i], iou3d[i], each (n).  One thread per pair on the device code of
+ * ws3d_boxes_overlap_bev; the BEV corners, the height overlap and the two divisions (clamp(min=1e-7) included) are evaluated in the
+ * kernel in torch's fp32 operation order, so all three outputs are bit for bit entry (i, i) of the n x n route -- n rotated
+ * intersections instead of n * n.                                                                                                  */
+WS3D_API int ws3d_boxes_iou3d_paired(int n, const float *boxes_a, const float *boxes_b, float *overlap_bev, float *iou2d, float *iou3d,
+                                     ws3d_stream_t stream);
+
 /* The K12/K13 mask alone (iou3d_kernel.cu:250-292 / 306-348): mask (n, ceil(n/64))
  * uint64, bit t of word c of row i = iou(box_i, box_{64c+t}) > thresh (diagonal
  * block: only t > i%64).  Words of blocks c < i/64 (never read by the sweep,
@@ -749,6 +757,30 @@ WS3D_API int ws3d_stage2_boxes(int rows, int loc_bins, int head_bins, float loc_
 WS3D_API int ws3d_stage2_select(int batch, int slots, float cls_thresh, float iou_thresh, const float *size_window, float ground_y,
                                 const float *box_ce, const float *rcnn_ref, const float *rcnn_cls, const float *rcnn_iou, const float *center,
                                 const int32_t *num, float *boxes, int32_t *keep, float *key, ws3d_stream_t stream);
+
+/* The Stage-2 training losses (lib/net/train_functions.py:230-516, lib/utils/loss_utils.py:151-338 with LOC_XZ_FINE = LOC_Y_BY_BIN =
+ * get_ry_fine = False), value AND gradient in one launch of one workgroup each: no host branch on fg_sum / iou_sum, no read-back, no
+ * atomics, sums folded in a fixed order (a call is bit-reproducible).  Row terms in float64 from the fp32 inputs; the paired 3-D IoU
+ * inside is the device function of ws3d_boxes_iou3d_paired.  An empty selection (no foreground row, ...) contributes an exact 0.
+ *
+ * ws3d_stage2_rcnn_loss: rcnn_cls (rows), rcnn_reg (rows, 4 loc_bins + 1 + 2 head_bins + 3), pred_boxes3d / gt_boxes (rows, 7)
+ * [x, y_bottom, z, h, w, l, ry], cls (rows) labels (> 0 foreground, 0 background, < 0 ignored by the classification term) ->
+ *   vals (8) = rcnn_loss_cls, 20 loc, angle, 300 size, 10 corner, rcnn_loss_reg = loc + angle + size, rcnn_loss = cls + reg + corner, 0
+ *   counts (4) int32 = fg_sum, iou_sum (foreground rows with iou3d(pred, gt) > 0.5), rows with cls >= 0, rows with cls == 0
+ *   grad_cls (rows), grad_reg (rows, width) = d rcnn_loss / d rcnn_cls, d rcnn_reg (pred_boxes3d is a constant: the corner term has a
+ *   value and no gradient, as in the reference, which detaches it).                                                                  */
+WS3D_API int ws3d_stage2_rcnn_loss(int rows, int loc_bins, int head_bins, float loc_scope, float h, float w, float l, const float *rcnn_cls,
+                                   const float *rcnn_reg, const float *pred_boxes3d, const float *gt_boxes, const float *cls, float *vals,
+                                   int32_t *counts, float *grad_cls, float *grad_reg, ws3d_stream_t stream);
+/* ws3d_stage2_ioun_loss: rcnn_iou (rows), rcnn_ref (rows, 7), pred_boxes3d / refined_box / gt_boxes (rows, 7), cls (rows) ->
+ *   vals (8) = 300 loc, 300 size, 20 angle, loss_iou = 100 mse(rcnn_iou, iou3d(refined_box, gt)^2) over the rows whose gt box has a
+ *   non-zero entry (the reference: whose entries do not SUM to 0 -- the same rows unless a box cancels to exactly zero, which would
+ *   depend on the summation order; 0 when there is none: the reference's mean over an empty selection is NaN), loss_reg, rcnn_loss_iou = loss_iou + loss_reg, 0, 0
+ *   counts (4) int32 = fg_sum, rows with a non-zero gt box, 0, 0
+ *   grad_iou (rows), grad_ref (rows, 7) = d rcnn_loss_iou / d rcnn_iou, d rcnn_ref.                                                  */
+WS3D_API int ws3d_stage2_ioun_loss(int rows, const float *rcnn_iou, const float *rcnn_ref, const float *pred_boxes3d, const float *refined_box,
+                                   const float *gt_boxes, const float *cls, float *vals, int32_t *counts, float *grad_iou, float *grad_ref,
+                                   ws3d_stream_t stream);
 
 #ifdef __cplusplus
 }

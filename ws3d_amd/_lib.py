@@ -96,6 +96,7 @@ SIGNATURES = {
     "ws3d_rowmax_bias_act": (_i, [_i, _i, C.c_long, _i, _i, _vp, _vp, _vp, _vp]),
     "ws3d_boxes_overlap_bev": (_i, [_i, _vp, _i, _vp, _vp, _vp]),
     "ws3d_boxes_iou_bev": (_i, [_i, _vp, _i, _vp, _vp, _vp]),
+    "ws3d_boxes_iou3d_paired": (_i, [_i, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_nms_mask": (_i, [_i, _vp, _f, _i, _i, _vp, _vp]),
     "ws3d_nms_workspace_bytes": (_sz, [_i]),
     "ws3d_nms": (_i, [_i, _vp, _f, _i, _i, _vp, _sz, _vp, _vp, _vp]),
@@ -142,6 +143,8 @@ SIGNATURES = {
     "ws3d_stage2_embed": (_i, [C.c_long, _i, _vp, _vp, _f] + [_vp] * 10 + [_vp, _vp, _vp]),
     "ws3d_stage2_boxes": (_i, [_i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ws3d_stage2_select": (_i, [_i, _i, _f, _f, C.POINTER(_f), _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws3d_stage2_rcnn_loss": (_i, [_i, _i, _i, _f, _f, _f, _f] + [_vp] * 9 + [_vp]),
+    "ws3d_stage2_ioun_loss": (_i, [_i] + [_vp] * 10 + [_vp]),
 }
 
 

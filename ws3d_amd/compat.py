@@ -1307,6 +1307,22 @@ def boxes_iou_bev_gpu(boxes_a, boxes_b, ans_iou):
     return 1
 
 
+def boxes_iou3d_paired(boxes_a, boxes_b):
+    """boxes_a, boxes_b (n,7) [x, y_bottom, z, h, w, l, ry] -> (overlap_bev, iou2d, iou3d), each (n,): the diagonal of the n x n route
+    bit for bit (ws3d_boxes_iou3d_paired); n == 0 returns empty tensors without a launch"""
+    dev = _dev(boxes_a, boxes_b)
+    _f32(boxes_a, "boxes_a"); _f32(boxes_b, "boxes_b")
+    if boxes_a.dim() != 2 or boxes_a.size(1) != 7 or boxes_a.shape != boxes_b.shape:
+        raise ValueError("boxes_iou3d_paired: boxes must both be (n,7), got %s and %s" % (tuple(boxes_a.shape), tuple(boxes_b.shape)))
+    n = boxes_a.size(0)
+    out = torch.empty((3, n), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out[0], out[1], out[2]
+    with _on(dev):
+        check(_lib.load().ws3d_boxes_iou3d_paired(n, _p(boxes_a), _p(boxes_b), _p(out[0]), _p(out[1]), _p(out[2]), _stream()), "boxes_iou3d_paired")
+    return out[0], out[1], out[2]
+
+
 def nms_device(boxes, thresh, normal=False, max_keep=0):
     """Device-resident NMS: boxes (n,5) score-sorted -> (keep int64 (n,) DEVICE, num int32 (1,)
     DEVICE).  No host synchronisation (ws3d extension used by the Stage-1 pipeline).
@@ -1582,6 +1598,57 @@ def stage2_select(box_ce, rcnn_ref, rcnn_cls, rcnn_iou, center, num, cls_thresh,
         check(_lib.load().ws3d_stage2_select(B, K, float(cls_thresh), float(iou_thresh), win, float(ground_y), _p(box_ce), _p(rcnn_ref), _p(rcnn_cls),
                                              _p(rcnn_iou), _p(center), _p(num), _p(boxes), _p(keep), _p(key), _stream()), "stage2_select")
     return boxes, keep, key
+
+
+def _loss_outputs(dev, shapes, out):
+    """(vals (8,) float32, counts (4,) int32, the gradient tensors): freshly allocated, or the caller's `out` tuple of the same layout"""
+    if out is None:
+        return (torch.empty((8,), dtype=torch.float32, device=dev), torch.empty((4,), dtype=torch.int32, device=dev),
+                *[torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes])
+    want = [((8,), torch.float32), ((4,), torch.int32)] + [(sh, torch.float32) for sh in shapes]
+    if len(out) != len(want) or any(tuple(t.shape) != sh or t.dtype != dt for t, (sh, dt) in zip(out, want)):
+        raise ValueError("loss outputs must be %s" % (want,))
+    _dev(*out)
+    return tuple(out)
+
+
+def stage2_rcnn_loss(rcnn_cls, rcnn_reg, pred_boxes3d, gt_boxes, cls, loc_scope, loc_bin_size, num_head_bin, mean_size, out=None):
+    """rcnn_cls (R,), rcnn_reg (R, 4*bins + 1 + 2*num_head_bin + 3), pred_boxes3d (R,7), gt_boxes (R,7), cls (R,) ->
+    (vals (8,), counts (4,) int32, grad_cls (R,), grad_reg (R,width)) as ws3d_stage2_rcnn_loss lays them out; no host synchronisation"""
+    dev = _dev(rcnn_cls, rcnn_reg, pred_boxes3d, gt_boxes, cls)
+    for t, name in ((rcnn_cls, "rcnn_cls"), (rcnn_reg, "rcnn_reg"), (pred_boxes3d, "pred_boxes3d"), (gt_boxes, "gt_boxes"), (cls, "cls")):
+        _f32(t, name)
+    bins = int((loc_scope + 1e-3) / loc_bin_size) * 2          # loss_utils.py:170, the expression of stage2_losses' torch route
+    width = 4 * bins + 1 + 2 * num_head_bin + 3
+    R = rcnn_cls.size(0)
+    if (tuple(rcnn_cls.shape) != (R,) or tuple(rcnn_reg.shape) != (R, width) or tuple(pred_boxes3d.shape) != (R, 7) or tuple(gt_boxes.shape) != (R, 7)
+            or tuple(cls.shape) != (R,)):
+        raise ValueError("stage2_rcnn_loss: shapes must be (R,) (R,%d) (R,7) (R,7) (R,)" % width)
+    vals, counts, g_cls, g_reg = _loss_outputs(dev, [(R,), (R, width)], out)
+    h, w, l = mean_size
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_rcnn_loss(R, bins, int(num_head_bin), float(loc_scope), float(h), float(w), float(l), _p(rcnn_cls), _p(rcnn_reg),
+                                                _p(pred_boxes3d), _p(gt_boxes), _p(cls), _p(vals), _p(counts), _p(g_cls), _p(g_reg), _stream()),
+              "stage2_rcnn_loss")
+    return vals, counts, g_cls, g_reg
+
+
+def stage2_ioun_loss(rcnn_iou, rcnn_ref, pred_boxes3d, refined_box, gt_boxes, cls, out=None):
+    """rcnn_iou (R,), rcnn_ref (R,7), pred_boxes3d / refined_box / gt_boxes (R,7), cls (R,) ->
+    (vals (8,), counts (4,) int32, grad_iou (R,), grad_ref (R,7)) as ws3d_stage2_ioun_loss lays them out; no host synchronisation"""
+    dev = _dev(rcnn_iou, rcnn_ref, pred_boxes3d, refined_box, gt_boxes, cls)
+    for t, name in ((rcnn_iou, "rcnn_iou"), (rcnn_ref, "rcnn_ref"), (pred_boxes3d, "pred_boxes3d"), (refined_box, "refined_box"),
+                    (gt_boxes, "gt_boxes"), (cls, "cls")):
+        _f32(t, name)
+    R = rcnn_iou.size(0)
+    if (tuple(rcnn_iou.shape) != (R,) or tuple(cls.shape) != (R,)
+            or any(tuple(t.shape) != (R, 7) for t in (rcnn_ref, pred_boxes3d, refined_box, gt_boxes))):
+        raise ValueError("stage2_ioun_loss: shapes must be (R,) (R,7) (R,7) (R,7) (R,7) (R,)")
+    vals, counts, g_iou, g_ref = _loss_outputs(dev, [(R,), (R, 7)], out)
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_ioun_loss(R, _p(rcnn_iou), _p(rcnn_ref), _p(pred_boxes3d), _p(refined_box), _p(gt_boxes), _p(cls), _p(vals),
+                                                _p(counts), _p(g_iou), _p(g_ref), _stream()), "stage2_ioun_loss")
+    return vals, counts, g_iou, g_ref
 
 
 def _default_device():

@@ -3,6 +3,7 @@
 //                       merge_down (256 -> 128) of a 64-point tile in one kernel (lib/net/rcnn_net.py:253-267, 337-365)
 //   ws3d_stage2_boxes   rcnn_reg -> the decoded box and its centre form (rcnn_net.py:293-308)
 //   ws3d_stage2_select  the element-wise part of the detection tail (rcnn_net.py:387-390, tools/eval_auto.py:397-436)
+// (the training losses ws3d_stage2_rcnn_loss / ws3d_stage2_ioun_loss are in stage2_loss.hip)
 #include <math.h>
 
 #include "common.h"

@@ -38,6 +38,14 @@ def boxes_iou3d_gpu(boxes_a, boxes_b):
     return iou2d, iou3d
 
 
+def boxes_iou3d_paired(boxes_a, boxes_b):
+    """(n,7),(n,7) [x,y,z,h,w,l,ry] -> (iou2d, iou3d), each (n,): pair i against pair i, bit for bit the diagonal of
+    ``boxes_iou3d_gpu(boxes_a, boxes_b)`` at n instead of n * n rotated intersections.  The BEV corners, the height overlap and the two
+    divisions are done in the kernel (contraction off, the operation order of ``boxes_iou3d_gpu`` above, clamp(min=1e-7) included)."""
+    _, iou2d, iou3d = _C.boxes_iou3d_paired(boxes_a.contiguous(), boxes_b.contiguous())
+    return iou2d, iou3d
+
+
 def _nms(boxes, scores, thresh, normal):
     # stable=True: equal scores keep their input order on every device (the reference's
     # unstable sort, iou3d_utils.py:67, is only reproducible for distinct scores)

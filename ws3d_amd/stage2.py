@@ -14,7 +14,9 @@ Two routes through the network:
     query, compact pairs, P = feats . W_f as one row GEMM, then ``ws3d_pgather_gemm3_compact`` or, where that entry returns
     WS3D_E_UNSUPPORTED, ``ws3d_pgather_gemm2_compact`` + ``ws3d_gemm_pool_compact``: ``sa_forward`` reads the return code at every
     call, nothing is latched per model), the GroupAll level and the heads as row GEMMs; ``ws3d_stage2_boxes`` between the towers.
-Training inputs (iou_trans / iou_scale / iou_ry) and the losses are not implemented.
+Training: ``towers='rcnn'`` is phase 1 (the reference with IOUN.ENABLED = False), ``freeze_rcnn_tower`` + the optional inputs
+iou_trans / iou_scale / iou_ry (noise on the box the IoU tower is given, rcnn_net.py:325-335) are phase 2; the losses are in
+``stage2_losses``, the driver is ``train_rcnn``.  Training runs the module route (the channels-last route keeps nothing for backward).
 """
 from __future__ import annotations
 
@@ -66,6 +68,8 @@ class RCNNConfig:
 
 
 DEFAULT_CFG = RCNNConfig()
+IOU_TOWER_PREFIXES = ("can_xyz_up_layer.", "can_feature_up_layer.", "can_merge_down_layer.", "SA_score_modules.", "ATT_score_modules.",
+                      "IOU_layer.", "ICL_layer.", "ref_layer.")      # what the reference creates after it freezes the rest (rcnn_net.py:126-196)
 
 # eval-mode GPU inference runs the channels-last route ``fast_forward`` (same weights and operators, (R,P,C) feature rows, the
 # tower fronts and the box decode on csrc/stage2.hip); clear to force the module route
@@ -152,6 +156,16 @@ def canonical_points(xyz, box_ce, extend=1.2):
     can = torch.stack((cx, cy, cz), dim=-1)
     out = can.abs().amax(dim=-1, keepdim=True) > extend
     return torch.where(out, torch.zeros_like(can), can)
+
+
+def noised_box(pred_ce, input_data, stage):
+    """the training noise on the box cascade stage `stage` is given (rcnn_net.py:325-335): centre += iou_trans (R,1,3,C), sizes *=
+    iou_scale (R,1,1,C), ry += iou_ry (R,1,1,C); the box itself when the keys are absent"""
+    if 'iou_trans' not in input_data:
+        return pred_ce
+    R = pred_ce.shape[0]
+    trans, scale, ry = (input_data[k][..., stage].to(pred_ce) for k in ('iou_trans', 'iou_scale', 'iou_ry'))
+    return torch.cat((pred_ce[:, 0:3] + trans.reshape(R, 3), pred_ce[:, 3:6] * scale.reshape(R, -1), pred_ce[:, 6:7] + ry.reshape(R, 1)), dim=1).contiguous()
 
 
 def supported(model: "RCNNNet") -> bool:
@@ -275,10 +289,23 @@ class RCNNNet(nn.Module):
             l_features.append(li_features)
         return l_features[-1]
 
-    def forward(self, input_data, box_ce=None, trace=None):
-        """input_data: cur_box_point (R,P,3), cur_box_reflect (R,P,1), train_mask (R,P,1) [, cur_pts_feature (R,P,128)].
+    def freeze_rcnn_tower(self):
+        """phase 2: ``requires_grad = False`` on everything the reference creates before its IoU modules (rcnn_net.py:126-128);
+        -> the names of the parameters that stay trainable"""
+        kept = []
+        for name, p in self.named_parameters():
+            p.requires_grad = name.startswith(IOU_TOWER_PREFIXES)
+            if p.requires_grad:
+                kept.append(name)
+        return kept
+
+    def forward(self, input_data, box_ce=None, trace=None, towers='both'):
+        """input_data: cur_box_point (R,P,3), cur_box_reflect (R,P,1), train_mask (R,P,1) [, cur_pts_feature (R,P,128)]
+        [, iou_trans (R,1,3,C), iou_scale (R,1,1,C), iou_ry (R,1,1,C): ``noised_box``; pred_boxes3d and refined_box follow the noised box].
         box_ce: optional (R,7) boxes for the IoU tower instead of the RCNN tower's own (teacher forcing; tests).
         trace: optional list; receives per grouped level of both towers a dict with the level's sampling (``_trace_level``).
+        towers: 'both', or 'rcnn' = the RCNN tower alone (IOUN.ENABLED = False): rcnn_cls, rcnn_reg and pred_boxes3d (R,1,7) = the
+        decoded box itself, y at the bottom face (rcnn_net.py:307).
         -> rcnn_cls (R,1), rcnn_reg (R,52), pred_boxes3d (R,1,7), rcnn_iou (R,1), rcnn_ref (R,7), ioun_cls (R,1),
         refined_box (R,1,7), box_ce (R,7), canonical_xyz (R,P,3), plus the input dict."""
         xyz = input_data['cur_box_point']
@@ -288,14 +315,16 @@ class RCNNNet(nn.Module):
             if ok is None:
                 ok = self.__dict__["_fastpath_ok"] = supported(self)
             if ok:
-                return fast_forward(self, input_data, box_ce, trace)
+                return fast_forward(self, input_data, box_ce, trace, towers)
+        if towers not in ('both', 'rcnn'):
+            raise ValueError("towers must be 'both' or 'rcnn', got %r" % (towers,))
         if not self.training and xyz.is_cuda and xyz.shape[0] > MODULE_ROUTE_MAX_CLOUDS and trace is None:
             # eval on the GPU: the channels-first epilogue kernels behind Conv1d / SharedMLP take up to 65535 (cloud, channel) rows per launch
             parts = []
             for i0 in range(0, xyz.shape[0], MODULE_ROUTE_MAX_CLOUDS):
                 sl = slice(i0, i0 + MODULE_ROUTE_MAX_CLOUDS)
                 parts.append(self.forward({k: (v[sl] if torch.is_tensor(v) and v.shape[:1] == xyz.shape[:1] else v) for k, v in input_data.items()},
-                                          None if box_ce is None else box_ce[sl]))
+                                          None if box_ce is None else box_ce[sl], None, towers))
             ret = {k: torch.cat([p_[k] for p_ in parts], dim=0) for k in parts[0] if k not in input_data}
             ret.update(input_data)
             return ret
@@ -307,20 +336,29 @@ class RCNNNet(nn.Module):
             rcnn_cls = self.cls_layer(top).transpose(1, 2).contiguous().squeeze(dim=1)
             rcnn_reg = self.reg_layer(top).transpose(1, 2).contiguous().squeeze(dim=1)
             R = rcnn_reg.shape[0]
-            if box_ce is not None:
-                pred_ce = box_ce.view(R, 7)
-            else:
+            decoded = None
+            if towers == 'rcnn' and rcnn_reg.is_cuda and rcnn_reg.dtype == torch.float32 and not c.loc_y_by_bin:
+                # phase 1: the box the loss reads comes from ws3d_stage2_boxes, the same bits on both routes
+                from . import compat as _C
+                decoded, _ = _C.stage2_boxes(rcnn_reg.detach().contiguous(), c.loc_scope, c.loc_bin_size, c.num_head_bin, c.cls_mean_size)
+            elif box_ce is None or towers == 'rcnn':
                 mean_size = torch.from_numpy(np.asarray(c.cls_mean_size, dtype=np.float32)).to(rcnn_reg)
-                pred_ce = box2center_box(decode_bbox_target_stage_2(
+                decoded = decode_bbox_target_stage_2(
                     torch.zeros((R, 3), dtype=rcnn_reg.dtype, device=rcnn_reg.device), rcnn_reg.detach().view(R, -1), anchor_size=mean_size,
                     loc_scope=c.loc_scope, loc_bin_size=c.loc_bin_size, num_head_bin=c.num_head_bin, get_xz_fine=False,
-                    loc_y_scope=c.loc_y_scope, loc_y_bin_size=c.loc_y_bin_size, get_ry_fine=False))
+                    loc_y_scope=c.loc_y_scope, loc_y_bin_size=c.loc_y_bin_size, get_ry_fine=False)
             ret = {'rcnn_cls': rcnn_cls, 'rcnn_reg': rcnn_reg}
+            if towers == 'rcnn':
+                ret['pred_boxes3d'] = decoded.view(R, 1, 7)
+                ret.update(input_data)
+                return ret
+            pred_ce = box_ce.view(R, 7) if box_ce is not None else box2center_box(decoded)
             n_sa = len(self.SA_score_modules) // self.cascade
             rcnn_ref = None
             for s in range(self.cascade):
                 if s != 0:
                     pred_ce = refine_box(pred_ce, rcnn_ref.view(R, 7))
+                pred_ce = noised_box(pred_ce, input_data, s)
                 # (the reference feeds the IoU tower the raw reflectance + mask, never cur_pts_feature: rcnn_net.py:357)
                 xc, fc = self._front(xyz, raw_features, pred_ce, self.can_xyz_up_layer[s], self.can_feature_up_layer[s], self.can_merge_down_layer[s], None)
                 top = self._tower(xc, fc, self.SA_score_modules[s * n_sa:(s + 1) * n_sa], self.ATT_score_modules[s * n_sa:(s + 1) * n_sa], trace)
@@ -394,7 +432,7 @@ def _head_rows(rows, seq):
 
 
 @torch.no_grad()
-def fast_forward(model: RCNNNet, input_data, box_ce=None, trace=None):
+def fast_forward(model: RCNNNet, input_data, box_ce=None, trace=None, towers='both'):
     """``RCNNNet.forward`` over channels-last rows for an eval-mode model that ``supported`` accepts; same dict.  Padding slots
     (all-zero clouds) run through like any cloud."""
     from . import compat as _C
@@ -404,10 +442,16 @@ def fast_forward(model: RCNNNet, input_data, box_ce=None, trace=None):
     x0, f0 = _front_rows(model, pts5, None, model.xyz_up_layer, model.feature_up_layer, model.merge_down_layer)
     top = _tower_rows(x0, f0, model.SA_modules, trace)
     rcnn_cls, rcnn_reg = _head_rows(top, model.cls_layer), _head_rows(top, model.reg_layer)
+    if towers == 'rcnn':
+        decoded, _ = _C.stage2_boxes(rcnn_reg, c.loc_scope, c.loc_bin_size, c.num_head_bin, c.cls_mean_size)
+        ret = {'rcnn_cls': rcnn_cls, 'rcnn_reg': rcnn_reg, 'pred_boxes3d': decoded.view(R, 1, 7)}
+        ret.update(input_data)
+        return ret
     if box_ce is not None:
         pred_ce = box_ce.view(R, 7).contiguous()
     else:
         _, pred_ce = _C.stage2_boxes(rcnn_reg, c.loc_scope, c.loc_bin_size, c.num_head_bin, c.cls_mean_size)
+    pred_ce = noised_box(pred_ce, input_data, 0)
     xc, fc = _front_rows(model, pts5, pred_ce, model.can_xyz_up_layer[0], model.can_feature_up_layer[0], model.can_merge_down_layer[0])
     top = _tower_rows(xc, fc, model.SA_score_modules, trace)
     rcnn_iou, rcnn_ref, ioun_cls = _head_rows(top, model.IOU_layer[0]), _head_rows(top, model.ref_layer[0]), _head_rows(top, model.ICL_layer[0])
@@ -428,16 +472,23 @@ class Stage2Net(nn.Module):
         self.cfg = cfg
         self.rcnn_net = RCNNNet(num_classes=num_classes, num_point=num_point, input_channels=input_channels, use_xyz=use_xyz, cfg=cfg)
 
-    def load_part_ckpt(self, state: dict) -> int:
+    def load_part_ckpt(self, state: dict, allow_missing_iou: bool = False) -> int:
         """load the ``rcnn_net.*`` entries of a reference checkpoint (the whole dict or its ``model_state``); other prefixes
         (``rpn.*``) are ignored, the way tools/train_utils' load_part_ckpt ignores keys the model lacks.  Every key of this model
-        must be there.  -> number of tensors loaded"""
+        must be there -- except, with allow_missing_iou, the IoU tower's (``IOU_TOWER_PREFIXES``): a phase-1 reference checkpoint,
+        written with IOUN.ENABLED = False, has none of them, and they keep their initialisation.  -> number of tensors loaded"""
         state = state.get("model_state", state)
         own = {k: v for k, v in state.items() if k.startswith("rcnn_net.")}
-        self.load_state_dict(own, strict=True)
+        if not allow_missing_iou:
+            self.load_state_dict(own, strict=True)
+            return len(own)
+        result = self.load_state_dict(own, strict=False)
+        bad = [k for k in result.missing_keys if not k[len("rcnn_net."):].startswith(IOU_TOWER_PREFIXES)]
+        if bad or result.unexpected_keys:
+            raise RuntimeError("load_part_ckpt: missing keys outside the IoU tower %s, unexpected keys %s" % (bad, list(result.unexpected_keys)))
         return len(own)
 
-    def rcnn_forward(self, input_data):
+    def rcnn_forward(self, input_data, towers='both'):
         """(R,P,.) inputs, or (B,K,P,.) as ``stage1.stage2_inputs`` returns them (flattened to R = B K; outputs come back (R, ...))"""
         pts = input_data['cur_box_point']
         if pts.dim() == 4:
@@ -445,12 +496,12 @@ class Stage2Net(nn.Module):
             for k in ('cur_box_point', 'cur_box_reflect', 'train_mask', 'cur_pts_feature'):
                 if k in flat:
                     flat[k] = flat[k].reshape(-1, *flat[k].shape[2:])
-            out = self.rcnn_net(flat)
+            out = self.rcnn_net(flat, towers=towers)
             for k in ('cur_box_point', 'cur_box_reflect', 'train_mask', 'cur_pts_feature'):
                 if k in input_data:
                     out[k] = input_data[k]
             return out
-        return self.rcnn_net(input_data)
+        return self.rcnn_net(input_data, towers=towers)
 
     forward = rcnn_forward
 
