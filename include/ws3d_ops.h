@@ -691,6 +691,26 @@ WS3D_API int ws3d_instance_clouds_emit(int batch, int pts_num, int centres_num, 
                                        const float *pts, const float *score, const float *feats, const float *centres, const int32_t *num,
                                        const int64_t *offsets, float *rows, float *row_feats, int32_t *row_idx, ws3d_stream_t stream);
 
+/* ------------------------------------------------- click-driven annotation (no reference op: host numpy / torch) */
+
+/* The front of tools/eval_active.py (:187, 198-209, 656-675) for a padded batch: BEV clicks -> a soft foreground score per scene
+ * point and the jittered candidate centres that ws3d_instance_clouds then cuts around.  Additive to ABI 6.
+ *   pts (B,N,4); clicks (B,K,3), a click's y is never read; num (B) int32 clicks per scene or NULL (all K), clamped to 0..K;
+ *   offsets: side floats in HOST memory, 1 <= side <= 9, the jitter grid's steps (the reference: 0.1 * (m - 2), m = 0..4).
+ *   score (B,N) = click_gaussian_mask (:656-675) in fp32, nothing contracted: yh = py * gauss_height; per click k < num[b]
+ *   d = sqrtf((dx*dx + yh*yh) + dz*dz) with dx = px - cx, dz = pz - cz, t = clamp(d - gauss_status, 0, 100); near = min over k
+ *   starting from 100; score = expf(-0.5f * near * near / gauss_cov).  A scene without clicks scores expf(-5000 / gauss_cov)
+ *   everywhere, exactly 0 for the reference's gauss_cov = 1.5.
+ *   cand (B, side*side*K, 3) in the reference's order (:202-209, whole click lists concatenated, x offset outer, z offset inner):
+ *   slot j < side*side*num[b], g = j / num[b], k = j % num[b]: (cx_k + offsets[g / side], centre_y, cz_k + offsets[g % side]),
+ *   fp32 additions; slots at or past side*side*num[b] are all zero.  cand_num (B) int32 = side*side*num[b].
+ * EVERY output element is written.  No allocation, no host synchronisation, no atomics; two launches, capturable.  B == 0: nothing to
+ * do; K == 0: score and cand_num are written (zeros for gauss_cov = 1.5); N == 0: only cand / cand_num are written.  Non-finite
+ * inputs give unspecified values.                                                                                                    */
+WS3D_API int ws3d_click_prepare(int batch, int pts_num, int clicks_num, int side, const float *offsets, float gauss_height, float gauss_status,
+                                float gauss_cov, float centre_y, const float *pts, const float *clicks, const int32_t *num, float *score,
+                                float *cand, int32_t *cand_num, ws3d_stream_t stream);
+
 /* ------------------------------------------------- KITTI evaluation (kitti_object_eval_python) */
 
 /* Frames are CSR ranges: gt_off / dt_off (frames + 1) int32 offsets of each frame's ground truths / detections, out_off (frames + 1)

@@ -135,6 +135,7 @@ SIGNATURES = {
     "ws3d_instance_clouds": (_i, [_i, _i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_instance_clouds_count": (_i, [_i, _i, _i, _f, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_instance_clouds_emit": (_i, [_i, _i, _i, _i, _f, _i, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws3d_click_prepare": (_i, [_i, _i, _i, _i, _vp, _f, _f, _f, _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_kitti_overlaps": (_i, [_i, _i, _i, C.c_long, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_kitti_collect_scores": (_i, [_i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, C.c_double, _vp, _vp, _vp]),
     "ws3d_kitti_count_workspace_bytes": (_sz, [_i, _i]),

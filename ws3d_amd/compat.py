@@ -1532,6 +1532,39 @@ def instance_clouds_emit(pts, score, feats, centres, num, radius, mask_mode, mas
     return 1
 
 
+# ------------------------------------------------------------------ click-driven annotation (csrc/click.hip)
+CLICK_LDS_CHUNK = 256       # clicks the score kernel stages per trip (CLICK_CHUNK of csrc/click.hip); K is unbounded
+CLICK_MAX_SIDE = 9
+
+
+def click_prepare(pts, clicks, num, offsets, gauss_height, gauss_status, gauss_cov, centre_y, score, cand, cand_num):
+    """ws3d_click_prepare: pts (B,N,4), clicks (B,K,3), num (B) int32 or None (all K), offsets: a sequence of ``side`` host floats
+    (rounded to fp32) -> score (B,N) the Gaussian of the distance to the nearest click, cand (B, side*side*K, 3) the jittered
+    candidates in the reference's order, cand_num (B) int32.  tools/eval_active.py:187, 198-209, 656-675.  ws3d extension."""
+    import ctypes
+    dev = _dev(pts, clicks, num, score, cand, cand_num)
+    _f32(pts, "pts"); _f32(clicks, "clicks"); _f32(score, "score"); _f32(cand, "cand"); _i32(cand_num, "cand_num")
+    side = len(offsets)
+    if not 1 <= side <= CLICK_MAX_SIDE:
+        raise Ws3dError(f"click_prepare: 1..{CLICK_MAX_SIDE} offsets expected, got {side}")
+    if pts.dim() != 3 or pts.size(2) != 4 or clicks.dim() != 3 or clicks.size(0) != pts.size(0) or clicks.size(2) != 3:
+        raise Ws3dError(f"click_prepare: pts (B,N,4), clicks (B,K,3) expected, got {tuple(pts.shape)} {tuple(clicks.shape)}")
+    B, N, K = pts.size(0), pts.size(1), clicks.size(1)
+    if num is not None:
+        _i32(num, "num")
+        if tuple(num.shape) != (B,):
+            raise Ws3dError(f"click_prepare: num (B) expected, got {tuple(num.shape)}")
+    if tuple(score.shape) != (B, N) or tuple(cand.shape) != (B, side * side * K, 3) or tuple(cand_num.shape) != (B,):
+        raise Ws3dError(f"click_prepare: score (B,N), cand (B,side*side*K,3), cand_num (B) expected, got {tuple(score.shape)} "
+                        f"{tuple(cand.shape)} {tuple(cand_num.shape)}")
+    off = (ctypes.c_float * side)(*[float(o) for o in offsets])
+    with _on(dev):
+        check(_lib.load().ws3d_click_prepare(B, N, K, side, ctypes.cast(off, ctypes.c_void_p), float(gauss_height), float(gauss_status),
+                                             float(gauss_cov), float(centre_y), _p(pts), _p(clicks), _p(num), _p(score), _p(cand),
+                                             _p(cand_num), _stream()), "click_prepare")
+    return 1
+
+
 # ------------------------------------------------------------------ Stage-2 box network (csrc/stage2.hip)
 def stage2_embed(pts, box_ce, wx0, bx0, wx1, bx1, wf0, bf0, wf1, bf1, wm, bm, extend=1.2):
     """pts (R,P,5) rows [x, y, z, reflectance, mask], box_ce (R,7) or None, the five layers' W^T (3,128) (128,128) (2,128) (128,128)

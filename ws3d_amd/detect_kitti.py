@@ -22,6 +22,17 @@ from . import kitti_io, stage1, stage2
 OUT_KEYS = ("rcnn_cls", "rcnn_iou", "rcnn_ref", "box_ce")
 
 
+def load_stage2(rcnn_ckpt=None, device="cuda:0", rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG, num_point: int = 512):
+    """Stage 2 alone (``annotate_kitti`` needs no Stage 1): from a reference checkpoint's ``rcnn_net.*`` keys or the seeded initialisation"""
+    from .seeded import seeded_state_dict
+    s2 = stage2.Stage2Net(mode="TEST", cfg=rcnn_cfg, num_point=num_point).to(torch.device(device)).eval()
+    if rcnn_ckpt:
+        s2.load_part_ckpt(torch.load(rcnn_ckpt, map_location="cpu"))
+    else:
+        s2.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in s2.state_dict().items()}, 0))
+    return s2
+
+
 def load_models(ckpt=None, rcnn_ckpt=None, device="cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG):
     from .seeded import seeded_state_dict
     dev = torch.device(device)
@@ -32,12 +43,27 @@ def load_models(ckpt=None, rcnn_ckpt=None, device="cuda:0", cfg: stage1.RPNConfi
         s1.load_state_dict({k: v for k, v in state.items() if k.startswith("rpn.")}, strict=True)
     else:
         s1.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in s1.state_dict().items()}, 0))
-    s2 = stage2.Stage2Net(mode="TEST", cfg=rcnn_cfg, num_point=cfg.roi_sampled_pts).to(dev).eval()
-    if rcnn_ckpt:
-        s2.load_part_ckpt(torch.load(rcnn_ckpt, map_location="cpu"))
-    else:
-        s2.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in s2.state_dict().items()}, 0))
-    return s1, s2
+    return s1, load_stage2(rcnn_ckpt, device, rcnn_cfg, cfg.roi_sampled_pts)
+
+
+@torch.no_grad()
+def rcnn_over_real_slots(s2, inp: dict, rcnn_batch: int = 800) -> dict:
+    """``Stage2Net.rcnn_forward`` over the real slots (k < num[b]) of a ``stage2_inputs``-style dict (cur_box_point (B,K,S,3),
+    cur_box_reflect, train_mask, center (B,K,3), num (B)) in chunks of ``rcnn_batch`` clouds -> the OUT_KEYS rows for all B K slots,
+    zero in the padding: what ``stage2.detections`` reads.  One host synchronisation (the list of real slots).  Shared by
+    ``detect_batch`` and ``annotate.annotate_batch``."""
+    center, num = inp["center"], inp["num"]
+    B, K = center.shape[0], center.shape[1]
+    real = (torch.arange(K, device=num.device)[None, :] < num[:, None]).reshape(-1).nonzero().reshape(-1)     # (one synchronisation per batch)
+    widths = {"rcnn_cls": 1, "rcnn_iou": 1, "rcnn_ref": 7, "box_ce": 7}
+    full = {k: torch.zeros((B * K, w), dtype=torch.float32, device=center.device) for k, w in widths.items()}
+    flat = {k: inp[k].reshape(B * K, *inp[k].shape[2:]) for k in ("cur_box_point", "cur_box_reflect", "train_mask")}
+    for i0 in range(0, real.numel(), rcnn_batch):
+        sel = real[i0:i0 + rcnn_batch]
+        res = s2.rcnn_forward({k: v[sel].contiguous() for k, v in flat.items()})
+        for k in OUT_KEYS:
+            full[k][sel] = res[k].reshape(sel.numel(), -1)
+    return full
 
 
 @torch.no_grad()
@@ -46,18 +72,7 @@ def detect_batch(s1, s2, pts: torch.Tensor, cfg: stage1.RPNConfig = stage1.DEFAU
     """pts (B,N,4) scenes -> (boxes (B,K,7), scores (B,K), count (B,)): K = the largest number of centres Stage 1 keeps in a scene"""
     out = s1.rpn_forward({"pts_input": pts})
     inp = stage1.stage2_inputs(out, pts, cfg, sampled_pt_num=cfg.roi_sampled_pts, ground_y=rcnn_cfg.ground_y)
-    center, num = inp["center"], inp["num"]
-    B, K = center.shape[0], center.shape[1]
-    real = (torch.arange(K, device=num.device)[None, :] < num[:, None]).reshape(-1).nonzero().reshape(-1)     # (one synchronisation per batch)
-    widths = {"rcnn_cls": 1, "rcnn_iou": 1, "rcnn_ref": 7, "box_ce": 7}
-    full = {k: torch.zeros((B * K, w), dtype=torch.float32, device=pts.device) for k, w in widths.items()}
-    flat = {k: inp[k].reshape(B * K, *inp[k].shape[2:]) for k in ("cur_box_point", "cur_box_reflect", "train_mask")}
-    for i0 in range(0, real.numel(), rcnn_batch):
-        sel = real[i0:i0 + rcnn_batch]
-        res = s2.rcnn_forward({k: v[sel].contiguous() for k, v in flat.items()})
-        for k in OUT_KEYS:
-            full[k][sel] = res[k].reshape(sel.numel(), -1)
-    return stage2.detections(full, center, num, rcnn_cfg)
+    return stage2.detections(rcnn_over_real_slots(s2, inp, rcnn_batch), inp["center"], inp["num"], rcnn_cfg)
 
 
 def run(root: str, split: str, out_dir: str, batch: int = 4, ckpt: str | None = None, rcnn_ckpt: str | None = None, npoints: int = 16384,

@@ -524,12 +524,13 @@ def select_boxes(box_ce, rcnn_ref, rcnn_cls, rcnn_iou, center, num, cfg: RCNNCon
 
 
 @torch.no_grad()
-def detections(out: dict, center: torch.Tensor, num: torch.Tensor, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None):
+def detections(out: dict, center: torch.Tensor, num: torch.Tensor, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None, return_index: bool = False):
     """tools/eval_auto.py:397-444, 572-612 for a batch.  out: ``rcnn_forward``'s dict for R = B K clouds, center (B,K,3) the
     kept centres, num (B,) how many of the K slots of a scene are real.  Refined box with ry in (-pi, pi], shifted to the scene's
     frame; kept where sigmoid(rcnn_cls) > RCNN.SCORE_THRESH, rcnn_iou > IOUN.SCORE_THRESH (the raw value), the size window and
     k < num[b]; sorted by rcnn_iou descending; greedy keep while the largest BEV IoU against the kept boxes is < 0.01.
     -> boxes (B,K,7), scores (B,K) = rcnn_iou, count (B,), zero padded.  No host synchronisation on the GPU.
+    return_index: a fourth result, index (B,K) int64: the slot k of ``center`` every kept box came from, -1 in the padding.
     iou_fn: forces the scene-by-scene host loop ``detections_loop`` with that BEV IoU (CPU tensors have no other route)."""
     B, K = center.shape[0], center.shape[1]
     cls, iou = out['rcnn_cls'].reshape(B, K).contiguous(), out['rcnn_iou'].reshape(B, K).contiguous()
@@ -549,8 +550,13 @@ def detections(out: dict, center: torch.Tensor, num: torch.Tensor, cfg: RCNNConf
         # survivors are listed in ascending sorted position and the flagged boxes sort first: the real ones are a prefix
         real = (torch.arange(kept_idx.shape[1], device=kept_idx.device)[None, :] < kept_num[:, None]) & (kept_idx < flagged[:, None])
         boxes, scores, count, _ = _C.select_proposals(box_sorted, sc, kept_idx, real.sum(dim=1).to(torch.int32), K)
-        return boxes, scores, count
-    return detections_loop(*select_boxes(ce, ref, cls, iou, center, num, cfg), cfg, iou_fn)
+        if not return_index:
+            return boxes, scores, count
+        # kept_idx holds sorted positions (only its first kept_num entries are written), order the slot at every sorted position
+        slot = order.gather(1, kept_idx[:, :K].clamp(0, max(K - 1, 0))) if K else order
+        pad = torch.arange(K, device=slot.device)[None, :] >= count[:, None]
+        return boxes, scores, count, slot.masked_fill(pad, -1)
+    return detections_loop(*select_boxes(ce, ref, cls, iou, center, num, cfg), cfg, iou_fn, return_index)
 
 
 def box2center_box_from_pred(pred_boxes3d):
@@ -558,10 +564,11 @@ def box2center_box_from_pred(pred_boxes3d):
     return box2center_box(pred_boxes3d.reshape(-1, 7))
 
 
-def detections_loop(box, keep, key, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None):
+def detections_loop(box, keep, key, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None, return_index: bool = False):
     """the sort and the greedy sweep of ``detections`` scene by scene on the host, one synchronisation per scene, as the reference
     runs them.  iou_fn: (n,7) boxes -> (n,n) BEV IoU; default: the rotated-overlap kernel behind ``iou3d_ops.boxes_iou3d_gpu``,
-    which needs the boxes on the GPU (there is no CPU overlap in this package)."""
+    which needs the boxes on the GPU (there is no CPU overlap in this package).  return_index: also index (B,K) int64, the slot
+    of ``box`` every kept box came from, -1 in the padding."""
     if iou_fn is None:
         from . import iou3d_ops
         iou_fn = lambda b: iou3d_ops.boxes_iou3d_gpu(b, b)[0]       # noqa: E731
@@ -569,6 +576,7 @@ def detections_loop(box, keep, key, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None):
     boxes = torch.zeros((B, K, 7), dtype=box.dtype, device=box.device)
     scores = torch.zeros((B, K), dtype=box.dtype, device=box.device)
     count = torch.zeros((B,), dtype=torch.int64, device=box.device)
+    index = torch.full((B, K), -1, dtype=torch.int64, device=box.device)
     for b in range(B):
         sel = box[b][keep[b]]
         s = key[b][keep[b]]
@@ -576,6 +584,7 @@ def detections_loop(box, keep, key, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None):
             continue
         order = torch.argsort(-s, stable=True)
         sel, s = sel[order], s[order]
+        slot = keep[b].nonzero().reshape(-1)[order]
         kept = [0]
         if sel.shape[0] > 1:
             iou2d = iou_fn(sel).cpu()
@@ -583,5 +592,5 @@ def detections_loop(box, keep, key, cfg: RCNNConfig = DEFAULT_CFG, iou_fn=None):
                 if float(iou2d[kept, i].max()) < np.float32(cfg.nms_iou):
                     kept.append(i)
         n = len(kept)
-        boxes[b, :n], scores[b, :n], count[b] = sel[kept], s[kept], n
-    return boxes, scores, count
+        boxes[b, :n], scores[b, :n], count[b], index[b, :n] = sel[kept], s[kept], n, slot[kept]
+    return (boxes, scores, count, index) if return_index else (boxes, scores, count)
