@@ -2625,12 +2625,31 @@ def test_compact_pairs_path_is_bit_identical_to_the_dense_one(ops, B, N, M, ns, 
     assert (out[:, 64:].double() - want).abs().max().item() <= 2e-5 * max(want.abs().max().item(), 1.0) * np.sqrt(max(C, 96) / 96)
 
 
-@pytest.mark.parametrize("ns,widths,r", [(16, (16, 16, 32), 0.1), (32, (32, 32, 64), 0.5), (32, (32, 32, 64), 3.0), (16, (16, 16, 32), 0.001)])
-def test_sa1_compact_chain_is_bit_identical_to_the_grouped_one(ops, ns, widths, r):
+SA1_CHAIN_CASES = [
+    pytest.param(16, (16, 16, 32), 0.1, 2, 16384, 4096, 0, id="16-widths0-0.1"), pytest.param(32, (32, 32, 64), 0.5, 2, 16384, 4096, 0, id="32-widths1-0.5"),
+    pytest.param(32, (32, 32, 64), 3.0, 2, 16384, 4096, 0, id="32-widths2-3.0"), pytest.param(16, (16, 16, 32), 0.001, 2, 16384, 4096, 0, id="16-widths3-0.001"),
+    # the other two (widths, nsample) instantiations of the grouped and the list kernel
+    pytest.param(16, (32, 32, 64), 0.3, 2, 16384, 4096, 0, id="16-wide-0.3"), pytest.param(32, (16, 16, 32), 0.3, 2, 16384, 4096, 0, id="32-narrow-0.3"),
+    # 32 list rows = ONE tile: the compact total stays below a tile (rows behind the end repeat the last one), both prefetches of the
+    # compact kernel run off the end, every wave but one leaves in the prologue
+    pytest.param(16, (32, 32, 64), 1.0, 1, 256, 2, 0, id="one-tile-wide"), pytest.param(16, (16, 16, 32), 1.0, 1, 256, 2, 0, id="one-tile-narrow"),
+    # eight tiles for ONE four-wave workgroup (ws3d_tune sa1_wgs = 1): each wave walks two tiles, the second prefetched under the first
+    pytest.param(32, (32, 32, 64), 4.0, 1, 256, 8, 1, id="eight-tiles-wide"), pytest.param(32, (16, 16, 32), 4.0, 1, 256, 8, 1, id="eight-tiles-narrow")]
+
+
+@pytest.mark.parametrize("ns,widths,r,B,N,M,wgs", SA1_CHAIN_CASES)
+def test_sa1_compact_chain_is_bit_identical_to_the_grouped_one(ops, ns, widths, r, B, N, M, wgs):
     """ws3d_sa_mlp3_pool_compact (first level over the distinct pairs, rows built from xyz / new_xyz / the feature channel) gives
     exactly ws3d_sa_mlp3_pool on the grouped tensor of ws3d_query_and_group_nlc"""
+    prev = ops.c.tune("sa1_wgs", wgs)
+    try:
+        _sa1_chain_forms_agree(ops, ns, widths, r, B, N, M)
+    finally:
+        ops.c.tune("sa1_wgs", prev)
+
+
+def _sa1_chain_forms_agree(ops, ns, widths, r, B, N, M):
     rng = np.random.default_rng(19)
-    B, N, M = 2, 16384, 4096
     pc = synth.make_batch("lidar", B, N, 68)
     xyz = dev(pc[:, :, :3].copy()); feat = dev(pc[:, :, 3:4].copy())
     idx = torch.empty((B, M), dtype=torch.int32, device="cuda"); new_xyz = torch.empty((B, M, 3), device="cuda")
@@ -2656,6 +2675,7 @@ def test_sa1_compact_chain_is_bit_identical_to_the_grouped_one(ops, ns, widths, 
     assert bool((lists[:, :32] == -7.0).all()) and torch.equal(lists[:, 32:], dense)
     pairs = ops.c.compact_pairs(nbr)
     T = int(pairs[2].item())
+    assert B * M <= T <= B * M * ns and (B * M * ns > 32 or T < 32), T      # (the one-tile scene: fewer distinct pairs than a tile)
     for limit, runs in ((T - 1, "dense"), (T, "compact")):
         o2_ = torch.zeros((B * M, widths[2]), device="cuda")
         assert ops.c.sa_mlp3_pool_compact(xyz, new_xyz, feat, pairs, layers, o2_, 0, limit=limit)

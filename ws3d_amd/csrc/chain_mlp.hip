@@ -26,14 +26,13 @@
 
 namespace ws3d {
 
-typedef float chain_f16 __attribute__((ext_vector_type(16)));
 #ifndef WS3D_CHAIN_G3
 #define WS3D_CHAIN_G3 1
 #endif
 constexpr int CHAIN_G3 = WS3D_CHAIN_G3;        // 32-channel blocks of the last layer accumulated per pass over k
 
 // accumulator tile (lane (p, h): register 4 q + i = channel 8 q + 4 h + i) -> ops[t] = (half 0: channel 2 t, half 1: channel 2 t + 1)
-__device__ __forceinline__ void chain_pair_operands(const chain_f16 &c, float (&ops)[16]) {
+__device__ __forceinline__ void chain_pair_operands(const floatx16 &c, float (&ops)[16]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         // permlane32_swap(a, b): lanes 32-63 of a <-> lanes 0-31 of b.  r[0] = (a.low, b.low), r[1] = (a.high, b.high)
@@ -85,7 +84,7 @@ __device__ __forceinline__ void chain3_tile(const ChainScale &a, const float *__
     const float *w1s = lds, *b1s = w1s + 256, *b2s = b1s + 64, *b3s = b2s + O2P;
     const float4 *w2l = reinterpret_cast<const float4 *>(b3s + 128), *w3l = w2l + 64 * O2P / 4;
     // ---- the rows: compact row -> (centre, source point) -> P row (64 channels: this half's 32) + centred coordinates
-    chain_f16 acc1[2];
+    floatx16 acc1[2];
     float bxy, bz;
     {
         const long t = min(tile * 32 + c, T - 1);            // rows behind the end repeat the last one (never pooled)
@@ -128,7 +127,7 @@ __device__ __forceinline__ void chain3_tile(const ChainScale &a, const float *__
     // ---- layer 2 (transposed): 32 k-steps, J2 output blocks
     float ops2[J2][16];
     {
-        chain_f16 acc2[J2];
+        floatx16 acc2[J2];
 #pragma unroll
         for (int jo = 0; jo < J2; ++jo)
 #pragma unroll
@@ -170,7 +169,7 @@ __device__ __forceinline__ void chain3_tile(const ChainScale &a, const float *__
     compact_centres16(a.rowc, tile * 32 + 16 * h, T, cen);
 #pragma unroll
     for (int g = 0; g < 4 / CHAIN_G3; ++g) {
-        chain_f16 acc3[CHAIN_G3];
+        floatx16 acc3[CHAIN_G3];
 #pragma unroll
         for (int j = 0; j < CHAIN_G3; ++j)
 #pragma unroll
@@ -310,18 +309,6 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_mlp3_pair_kernel(const Ch
 
 }  // namespace ws3d
 
-static int chain_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
 static int chain_scale_from(const ws3d_compact_mlp_args &q, ws3d::ChainScale &a, bool rows) {
     const uintptr_t al = reinterpret_cast<uintptr_t>(q.pmat) | reinterpret_cast<uintptr_t>(q.out);
     bool ok = q.o1 == 64 && q.o2 > 0 && q.o2 <= 96 && q.o3 == 128 && q.w1x && q.w2t && q.w3t;
@@ -376,7 +363,7 @@ extern "C" int ws3d_chain_mlp3(const ws3d_compact_mlp_args *p0, const ws3d_compa
     }
     if (nscales == 1) { a[1] = a[0]; blob1 = blob0; }
     if (lds > 160 * 1024) { set_error("ws3d_chain_mlp3: %zu B of LDS", lds); return WS3D_E_UNSUPPORTED; }
-    long wgs = workgroups > 0 ? workgroups : (g_tune[TUNE_CHAIN_WGS] > 0 ? g_tune[TUNE_CHAIN_WGS] : chain_cu_count());
+    long wgs = workgroups > 0 ? workgroups : (g_tune[TUNE_CHAIN_WGS] > 0 ? g_tune[TUNE_CHAIN_WGS] : cu_count());
     wgs = std::max(1L, std::min(wgs, (max_tiles + CHAIN_THREADS / 64 - 1) / (CHAIN_THREADS / 64)));
     hipStream_t st = as_stream(stream);
 #define WS3D_CHAIN_GO(JA, JB)                                                                                                       \

@@ -19,6 +19,12 @@ int check_launch(const char *what);
 // of the current device: a process that drives several devices must raise it on each).  Remembered per (function, device) under a
 // mutex; a failure is reported through set_error / WS3D_E_LAUNCH.  No-op for bytes <= 64 KiB (the default cap).
 int raise_lds_cap(const void *fn, size_t bytes, const char *what);
+// Compute units of the CURRENT device (asked once per device; 256 if the runtime does not say): what the launchers that size a
+// grid by the machine ("one workgroup per CU", "more scenes than CUs") go by.
+int cu_count();
+
+// the 32 x 32 fp32 accumulator of the matrix instructions (v_mfma_f32_32x32x2_f32, v_mfma_f32_32x32x16_bf16): 16 registers per lane
+typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // Launch-geometry knobs (ws3d_tune, include/ws3d_ops.h): 0 = the built-in choice.  Speed only: every kernel that reads one is complete
 // for any value (persistent workgroups walking tiles).

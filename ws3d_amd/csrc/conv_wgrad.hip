@@ -7,10 +7,9 @@
 // (v_mfma_f32_32x32x2_f32, fp32 in / fp32 accumulate) over one (scene, l-range) slice of K, the slices'
 // partial tiles go to a workspace and a second kernel adds them in a FIXED order: deterministic.
 #include "common.h"
+#include "mfma_tile.h"
 
 namespace ws3d {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 // ROWS rows of each operand are staged per tile (64, or 16 for layers with <= 16 channels on both sides),
 // KT values of l per row: 128 / 256 contiguous bytes per row and tile -- with 64-byte pieces (KT = 16) the
@@ -87,14 +86,14 @@ __global__ __launch_bounds__(256) void conv_wgrad_partial_kernel(int o_dim, int 
             __syncthreads();
         }
     }
-    // register v of lane l holds row (o) 8*(v/4) + 4*(l/32) + v%4, column (c) l%32 of the wave's 32 x 32 sub-tile
+    // register v of lane l holds row (o) acc_row(v, l / 32), column (c) l % 32 of the wave's 32 x 32 sub-tile
     if (!mfma_wave) return;
     float *pt = partial + (size_t)blockIdx.z * o_dim * c_dim;
     const int cc = c0 + (ROWS == 64 ? wn * 32 : 0) + (lane & 31);
     const bool c_ok = cc < c_dim && (ROWS == 64 || (lane & 31) < ROWS);
 #pragma unroll
     for (int v = 0; v < 16; ++v) {
-        const int ro = 8 * (v / 4) + 4 * (lane >> 5) + (v & 3);
+        const int ro = acc_row(v, lane >> 5);
         const int oo = o0 + (ROWS == 64 ? wm * 32 : 0) + ro;
         if (oo < o_dim && c_ok && (ROWS == 64 || ro < ROWS)) pt[(size_t)oo * c_dim + cc] = acc[v];
     }

@@ -48,6 +48,18 @@ int raise_lds_cap(const void *fn, size_t bytes, const char *what) {
     return WS3D_OK;
 }
 
+int cu_count() {
+    static int cus[64] = {0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (cus[dev] == 0) {
+        int n = 0;
+        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
+        cus[dev] = n;
+    }
+    return cus[dev];
+}
+
 }  // namespace ws3d
 
 extern "C" int ws3d_abi_version(void) { return WS3D_ABI_VERSION; }

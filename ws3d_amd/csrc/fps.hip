@@ -691,13 +691,7 @@ bool fps_v3_launch(int b, int n, int m, const float *xyz, float *temp, int32_t *
 static bool fps_pair_mode(int b) {
     static const int env = getenv("WS3D_FPS_PAIR") ? atoi(getenv("WS3D_FPS_PAIR")) : -1;
     if (env >= 0) return env != 0;
-    static int cus = 0;
-    if (!cus) {
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    }
-    return b > cus;
+    return b > cu_count();
 }
 
 static int fps_dispatch(int b, int n, int m, const float *xyz, float *temp, int32_t *idx,

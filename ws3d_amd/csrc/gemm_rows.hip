@@ -3,10 +3,8 @@
 // those run at the fp32 MFMA roof (v_mfma_f32_32x32x2_f32) once 20 graphs are in flight, and only a cheaper product moves that roof
 // (DESIGN.md section 10.3).
 //
-// The split product (as csrc/rpn_heads.hip): every fp32 operand is written as three bf16 pieces,
-// x = x1 + x2 + x3 (+ a remainder below 2^-24 |x|), and the six largest of the nine partial products are summed on
-// v_mfma_f32_32x32x16_bf16 into one fp32 accumulator, smallest first: w3 a1, w2 a2, w1 a3, w2 a1, w1 a2, w1 a1.  6 / 16 of the fp32
-// instruction's time per product.
+// The product is the split-bf16 one of split_bf16.h (as csrc/rpn_heads.hip): three bf16 pieces per fp32
+// operand, six products per k-step on v_mfma_f32_32x32x16_bf16 into one fp32 accumulator.
 //
 // Geometry.  A workgroup of four waves computes one tile of 64 rows x 128 columns (128 x 128 from 512 such tiles on; N % 128 != 0:
 // 64 x 64), TRANSPOSED like the heads: the MFMA's A operand is the weights (row = output column), its B operand the rows of A (col =
@@ -28,11 +26,10 @@
 // Bias is added in fp32 after the accumulation; the ReLU keeps a NaN (a row that holds Inf / NaN gives non-finite outputs in that row
 // only: its pieces meet the other rows' columns of the MFMA's B operand nowhere).
 #include "common.h"
+#include "split_bf16.h"
 
 namespace ws3d {
 
-typedef float rows_f16 __attribute__((ext_vector_type(16)));
-typedef __bf16 rows_bf8 __attribute__((ext_vector_type(8)));
 typedef unsigned rows_u4 __attribute__((ext_vector_type(4)));      // 16 bytes of the packed image
 typedef float rows_f4 __attribute__((ext_vector_type(4)));
 
@@ -50,28 +47,6 @@ __host__ __device__ constexpr int gr_a_stage(int tm) { return tm / 32 * 2 * 3 * 
 __host__ __device__ constexpr int gr_lds_bytes(int tm) { return 2 * gr_a_stage(tm); }              // double-buffered
 static_assert(gr_lds_bytes(128) <= 64 * 1024 && gr_lds_bytes(128) * 2 <= 160 * 1024, "inside the default per-workgroup cap, two workgroups per CU");
 
-// x = p1 + p2 + p3 (+ a remainder below 2^-24 |x|): each piece is the bf16 nearest to what the pieces before it left; every
-// subtraction is exact in fp32.  +-Inf gives (Inf, NaN, NaN), NaN three NaNs.
-__device__ __forceinline__ void rows_split3(float x, __bf16 &p1, __bf16 &p2, __bf16 &p3) {
-    p1 = (__bf16)x;
-    const float r1 = x - (float)p1;
-    p2 = (__bf16)r1;
-    const float r2 = r1 - (float)p2;
-    p3 = (__bf16)r2;
-}
-
-__device__ __forceinline__ void rows_split8(const float *v, rows_bf8 &q1, rows_bf8 &q2, rows_bf8 &q3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 p1, p2, p3;
-        rows_split3(v[j], p1, p2, p3);
-        q1[j] = p1; q2[j] = p2; q3[j] = p3;
-    }
-}
-
-// ReLU that keeps a NaN (fmaxf(NaN, 0) = 0 would turn a non-finite row into a finite output)
-__device__ __forceinline__ float rows_relu(float y) { return y < 0.f ? 0.f : y; }
-
 // one thread per (k-block, column block, k-step, lane): eight weights of one column -> the lane's 16 bytes of three fragments
 __global__ __launch_bounds__(256) void gemm_rows_pack_kernel(int K, int N, const float *__restrict__ wt, rows_u4 *__restrict__ pack) {
     const int nb_all = N / 32;
@@ -84,8 +59,8 @@ __global__ __launch_bounds__(256) void gemm_rows_pack_kernel(int K, int N, const
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] = wt[(long)(k0 + j) * N + col];
-        rows_bf8 q1, q2, q3;
-        rows_split8(v, q1, q2, q3);
+        bf16x8 q1, q2, q3;
+        split8(v, q1, q2, q3);
         rows_u4 *dst = pack + ((f * 2 + s) * 3) * 64 + lane;
         dst[0] = __builtin_bit_cast(rows_u4, q1);
         dst[64] = __builtin_bit_cast(rows_u4, q2);
@@ -118,7 +93,7 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gemm_rows_kernel(int K, int N, 
     const rows_u4 *wp = pack + (size_t)(tn * NBT + nbl) * 6 * 64 + lane;
     const size_t w_kb = (size_t)nb_all * 6 * 64;
 
-    rows_f16 acc[MBW];
+    floatx16 acc[MBW];
 #pragma unroll
     for (int m = 0; m < MBW; ++m)
 #pragma unroll
@@ -146,29 +121,18 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gemm_rows_kernel(int K, int N, 
             const unsigned char *buf = smem_rows + (kb & 1) * STAGE + lane * 16;
 #pragma unroll
             for (int s = 0; s < 2; ++s) {
-                const rows_bf8 w1 = __builtin_bit_cast(rows_bf8, wc[3 * s]), w2 = __builtin_bit_cast(rows_bf8, wc[3 * s + 1]),
-                               w3 = __builtin_bit_cast(rows_bf8, wc[3 * s + 2]);
-                rows_bf8 a1[MBW], a2[MBW], a3[MBW];
+                const bf16x8 w1 = __builtin_bit_cast(bf16x8, wc[3 * s]), w2 = __builtin_bit_cast(bf16x8, wc[3 * s + 1]),
+                               w3 = __builtin_bit_cast(bf16x8, wc[3 * s + 2]);
+                bf16x8 a1[MBW], a2[MBW], a3[MBW];
 #pragma unroll
                 for (int m = 0; m < MBW; ++m) {
                     const unsigned char *af = buf + ((mb0 + m) * 2 + s) * 3 * GR_FRAG;
-                    a1[m] = *reinterpret_cast<const rows_bf8 *>(af);
-                    a2[m] = *reinterpret_cast<const rows_bf8 *>(af + GR_FRAG);
-                    a3[m] = *reinterpret_cast<const rows_bf8 *>(af + 2 * GR_FRAG);
+                    a1[m] = *reinterpret_cast<const bf16x8 *>(af);
+                    a2[m] = *reinterpret_cast<const bf16x8 *>(af + GR_FRAG);
+                    a3[m] = *reinterpret_cast<const bf16x8 *>(af + 2 * GR_FRAG);
                 }
-                // the six products, smallest first; the row blocks' chains interleaved (each accumulator is summed in the same order)
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w3, a1[m], acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, a2[m], acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, a3[m], acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, a1[m], acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, a2[m], acc[m], 0, 0, 0);
-#pragma unroll
-                for (int m = 0; m < MBW; ++m) acc[m] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, a1[m], acc[m], 0, 0, 0);
+                // the row blocks' chains interleaved (each accumulator is summed in the same order)
+                split_mfma6<MBW>(w1, w2, w3, a1, a2, a3, acc);
             }
         }
         if (more) {
@@ -176,11 +140,11 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gemm_rows_kernel(int K, int N, 
 #pragma unroll
             for (int u = 0; u < UNITS; ++u) {
                 const float v[8] = {ra[u][0][0], ra[u][0][1], ra[u][0][2], ra[u][0][3], ra[u][1][0], ra[u][1][1], ra[u][1][2], ra[u][1][3]};
-                rows_bf8 q1, q2, q3;
-                rows_split8(v, q1, q2, q3);
-                *reinterpret_cast<rows_bf8 *>(nxt + u * 12 * GR_FRAG) = q1;                 // 64 rows = two row blocks of [k-step 2][piece 3] further
-                *reinterpret_cast<rows_bf8 *>(nxt + u * 12 * GR_FRAG + GR_FRAG) = q2;
-                *reinterpret_cast<rows_bf8 *>(nxt + u * 12 * GR_FRAG + 2 * GR_FRAG) = q3;
+                bf16x8 q1, q2, q3;
+                split8(v, q1, q2, q3);
+                *reinterpret_cast<bf16x8 *>(nxt + u * 12 * GR_FRAG) = q1;                 // 64 rows = two row blocks of [k-step 2][piece 3] further
+                *reinterpret_cast<bf16x8 *>(nxt + u * 12 * GR_FRAG + GR_FRAG) = q2;
+                *reinterpret_cast<bf16x8 *>(nxt + u * 12 * GR_FRAG + 2 * GR_FRAG) = q3;
             }
 #pragma unroll
             for (int i = 0; i < 6; ++i) wc[i] = wn[i];
@@ -206,7 +170,7 @@ __global__ __launch_bounds__(GR_THREADS, 2) void gemm_rows_kernel(int K, int N, 
             if (bias) y = y + b4[g];                              // fp32, after the accumulation (no bias: -0 stays -0)
             if (relu) {
 #pragma unroll
-                for (int e = 0; e < 4; ++e) y[e] = rows_relu(y[e]);
+                for (int e = 0; e < 4; ++e) y[e] = relu_keep_nan(y[e]);
             }
             *reinterpret_cast<rows_f4 *>(orow + 8 * g) = y;
         }

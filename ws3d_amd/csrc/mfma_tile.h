@@ -8,12 +8,9 @@
 // Arithmetic contract of every block: accumulators start where the caller says (zero, or the gathered row of P), k ascends, two
 // k per matrix instruction, zero padding behind the k extent, then bias -> ReLU -> max / store.
 #pragma once
-#include <hip/hip_runtime.h>
-#include <stdint.h>
+#include "common.h"
 
 namespace ws3d {
-
-typedef float floatx16 __attribute__((ext_vector_type(16)));
 
 constexpr int GP_KT = 16;          // K step per LDS tile
 constexpr int GP_XS = 65;          // padded row length of a k-major 64-row tile

@@ -2,10 +2,8 @@
 // matrix cores at fp32 accuracy.  Replaces, where the shapes fit, the two ws3d_mlp2_rows launches (sa_mlp.hip), which run the same
 // two layers on v_mfma_f32_32x32x2_f32 at 64 cycles per k = 2 and are bound by it.
 //
-// The split product: every fp32 operand is written as three bf16 pieces, x = x1 + x2 + x3 (+ a remainder below
-// 2^-24 |x|), and the six largest of the nine partial products are summed on v_mfma_f32_32x32x16_bf16 (32 cycles per k = 16; a
-// bf16 x bf16 product is exact in the fp32 accumulator), smallest first: a3 b1, a2 b2, a1 b3, a2 b1, a1 b2, a1 b1.  The dropped
-// terms a2 b3, a3 b2, a3 b3 are below 2^-16 |a b| x 2^-8 each.  6 / 16 of the fp32 instruction's time per product.
+// The product is the split-bf16 one of split_bf16.h (three bf16 pieces per fp32 operand, six products per k-step on
+// v_mfma_f32_32x32x16_bf16).
 //
 // A workgroup serves ONE head (one head's split first layer takes 104 KB of LDS; both do not fit): the first wg_cls workgroups of
 // the grid the classification head, the others the regression head, each walking its head's 32-row tiles in chunks of 8 (one per
@@ -24,11 +22,9 @@
 #include <algorithm>
 
 #include "common.h"
+#include "split_bf16.h"
 
 namespace ws3d {
-
-typedef float heads_f16 __attribute__((ext_vector_type(16)));
-typedef __bf16 heads_bf8 __attribute__((ext_vector_type(8)));
 
 constexpr int HEADS_K = 128;                 // input channels = first-layer width
 constexpr int HEADS_KS = HEADS_K + 8;        // bf16 row stride of a packed matrix: 272 B, ds_read_b128 conflict-free over 32 rows
@@ -47,40 +43,6 @@ constexpr int HB_W2 = HB_B2 + 4 * HEADS_MAX_O2;
 __host__ __device__ constexpr int heads_blob_bytes(int o2) { return HB_W2 + (o2 == 1 ? 4 * HEADS_K : 3 * o2 * HEADS_KS * 2); }
 static_assert(HB_W2 % 16 == 0 && heads_blob_bytes(HEADS_MAX_O2) <= 160 * 1024, "rpn_heads blob layout");
 
-// x = p1 + p2 + p3 (+ a remainder below 2^-24 |x|): each piece is the bf16 nearest to what the pieces before it left; every
-// subtraction is exact in fp32.  +-Inf gives (Inf, NaN, NaN), NaN three NaNs.
-__device__ __forceinline__ void heads_split3(float x, __bf16 &p1, __bf16 &p2, __bf16 &p3) {
-    p1 = (__bf16)x;
-    const float r1 = x - (float)p1;
-    p2 = (__bf16)r1;
-    const float r2 = r1 - (float)p2;
-    p3 = (__bf16)r2;
-}
-
-__device__ __forceinline__ void heads_split8(const float *v, heads_bf8 &q1, heads_bf8 &q2, heads_bf8 &q3) {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        __bf16 p1, p2, p3;
-        heads_split3(v[j], p1, p2, p3);
-        q1[j] = p1; q2[j] = p2; q3[j] = p3;
-    }
-}
-
-// the six products of one k-step, smallest first; A = a matrix's pieces (w1 largest), B = the operand's pieces
-__device__ __forceinline__ heads_f16 heads_mfma6(const heads_bf8 &w1, const heads_bf8 &w2, const heads_bf8 &w3, const heads_bf8 &b1,
-                                                 const heads_bf8 &b2, const heads_bf8 &b3, heads_f16 c) {
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w3, b1, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b2, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b3, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w2, b1, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b2, c, 0, 0, 0);
-    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(w1, b1, c, 0, 0, 0);
-    return c;
-}
-
-// ReLU that keeps a NaN (fmaxf(NaN, 0) = 0 would turn a non-finite row into a finite output)
-__device__ __forceinline__ float heads_relu(float y) { return y < 0.f ? 0.f : y; }
-
 // packed k position kk (0 .. 127) of the regression head's second layer -> its input channel
 __host__ __device__ constexpr int heads_w2_channel(int kk) {
     return (kk & ~31) + 16 * ((kk >> 4) & 1) + 8 * ((kk & 7) >> 2) + 4 * ((kk >> 3) & 1) + (kk & 3);
@@ -98,7 +60,7 @@ __global__ __launch_bounds__(256) void rpn_heads_pack_kernel(int o2, const float
     for (int i = t; i < HEADS_K * HEADS_KS; i += nt) {
         const int o = i / HEADS_KS, k = i - o * HEADS_KS;
         __bf16 p1, p2, p3;
-        heads_split3(k < HEADS_K ? w1t[k * HEADS_K + o] : 0.f, p1, p2, p3);
+        split3(k < HEADS_K ? w1t[k * HEADS_K + o] : 0.f, p1, p2, p3);
         w1p[i] = p1; w1p[HEADS_K * HEADS_KS + i] = p2; w1p[2 * HEADS_K * HEADS_KS + i] = p3;
     }
     float *bb1 = reinterpret_cast<float *>(blob + HB_B1), *bb2 = reinterpret_cast<float *>(blob + HB_B2);
@@ -112,7 +74,7 @@ __global__ __launch_bounds__(256) void rpn_heads_pack_kernel(int o2, const float
         for (int i = t; i < o2 * HEADS_KS; i += nt) {
             const int o = i / HEADS_KS, kk = i - o * HEADS_KS;
             __bf16 p1, p2, p3;
-            heads_split3(kk < HEADS_K ? w2t[heads_w2_channel(kk) * o2 + o] : 0.f, p1, p2, p3);
+            split3(kk < HEADS_K ? w2t[heads_w2_channel(kk) * o2 + o] : 0.f, p1, p2, p3);
             w2p[i] = p1; w2p[o2 * HEADS_KS + i] = p2; w2p[2 * o2 * HEADS_KS + i] = p3;
         }
     }
@@ -142,22 +104,22 @@ __device__ __forceinline__ void rpn_head_walk(long tiles, const float *__restric
                 xv[8 * s] = t0.x; xv[8 * s + 1] = t0.y; xv[8 * s + 2] = t0.z; xv[8 * s + 3] = t0.w;
                 xv[8 * s + 4] = t1.x; xv[8 * s + 5] = t1.y; xv[8 * s + 6] = t1.z; xv[8 * s + 7] = t1.w;
             }
-            heads_f16 acc[4];
+            floatx16 acc[4];
 #pragma unroll
             for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[blk][i] = 0.f;
 #pragma unroll
             for (int s = 0; s < 8; ++s) {
-                heads_bf8 q1, q2, q3;
-                heads_split8(xv + 8 * s, q1, q2, q3);
+                bf16x8 q1, q2, q3;
+                split8(xv + 8 * s, q1, q2, q3);
 #pragma unroll
                 for (int blk = 0; blk < 4; ++blk) {
                     const __bf16 *wr = w1p + blk * 32 * HEADS_KS + 16 * s;
-                    const heads_bf8 a1 = *reinterpret_cast<const heads_bf8 *>(wr);
-                    const heads_bf8 a2 = *reinterpret_cast<const heads_bf8 *>(wr + PIECE1);
-                    const heads_bf8 a3 = *reinterpret_cast<const heads_bf8 *>(wr + 2 * PIECE1);
-                    acc[blk] = heads_mfma6(a1, a2, a3, q1, q2, q3, acc[blk]);
+                    const bf16x8 a1 = *reinterpret_cast<const bf16x8 *>(wr);
+                    const bf16x8 a2 = *reinterpret_cast<const bf16x8 *>(wr + PIECE1);
+                    const bf16x8 a3 = *reinterpret_cast<const bf16x8 *>(wr + 2 * PIECE1);
+                    split_mfma6<1>(a1, a2, a3, &q1, &q2, &q3, &acc[blk]);
                 }
             }
             // bias + ReLU: register v of block blk = channel blk * 32 + (v & 3) + 8 (v >> 2) + 4 h of row r
@@ -166,7 +128,7 @@ __device__ __forceinline__ void rpn_head_walk(long tiles, const float *__restric
 #pragma unroll
                 for (int v = 0; v < 16; ++v) {
                     const float y = acc[blk][v] + b1s[blk * 32 + (v & 3) + 8 * (v >> 2) + 4 * h];
-                    acc[blk][v] = relu1 ? heads_relu(y) : y;
+                    acc[blk][v] = relu1 ? relu_keep_nan(y) : y;
                 }
             if constexpr (NB2 == 0) {
                 const float *w2s = reinterpret_cast<const float *>(lds + HB_W2);
@@ -177,12 +139,12 @@ __device__ __forceinline__ void rpn_head_walk(long tiles, const float *__restric
                     for (int v = 0; v < 16; ++v) p = __builtin_fmaf(acc[blk][v], w2s[blk * 32 + (v & 3) + 8 * (v >> 2) + 4 * h], p);
                 const float q = __shfl_xor(p, 32);
                 float y = (h ? q + p : p + q) + b2s[0];          // half 0's sum + half 1's in both halves
-                if (relu2) y = heads_relu(y);
+                if (relu2) y = relu_keep_nan(y);
                 if (h == 0) out[tile * 32 + r] = y;
             } else {
                 const __bf16 *w2p = reinterpret_cast<const __bf16 *>(lds + HB_W2);
                 const int piece2 = o2 * HEADS_KS;
-                heads_f16 y[NB2];
+                floatx16 y[NB2];
 #pragma unroll
                 for (int ob = 0; ob < NB2; ++ob)
 #pragma unroll
@@ -191,20 +153,20 @@ __device__ __forceinline__ void rpn_head_walk(long tiles, const float *__restric
                 for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
                     for (int s = 0; s < 2; ++s) {
-                        heads_bf8 q1, q2, q3;
+                        bf16x8 q1, q2, q3;
                         float av[8];
 #pragma unroll
                         for (int j = 0; j < 8; ++j) av[j] = acc[blk][8 * s + j];
-                        heads_split8(av, q1, q2, q3);
+                        split8(av, q1, q2, q3);
 #pragma unroll
                         for (int ob = 0; ob < NB2; ++ob) {
                             // rows o >= o2 compute outputs nobody stores: they read the last row (no padding in the blob)
                             const int o = min(ob * 32 + r, o2 - 1);
                             const __bf16 *wr = w2p + o * HEADS_KS + blk * 32 + 16 * s + 8 * h;
-                            const heads_bf8 a1 = *reinterpret_cast<const heads_bf8 *>(wr);
-                            const heads_bf8 a2 = *reinterpret_cast<const heads_bf8 *>(wr + piece2);
-                            const heads_bf8 a3 = *reinterpret_cast<const heads_bf8 *>(wr + 2 * piece2);
-                            y[ob] = heads_mfma6(a1, a2, a3, q1, q2, q3, y[ob]);
+                            const bf16x8 a1 = *reinterpret_cast<const bf16x8 *>(wr);
+                            const bf16x8 a2 = *reinterpret_cast<const bf16x8 *>(wr + piece2);
+                            const bf16x8 a3 = *reinterpret_cast<const bf16x8 *>(wr + 2 * piece2);
+                            split_mfma6<1>(a1, a2, a3, &q1, &q2, &q3, &y[ob]);
                         }
                     }
                 // register v of block ob = output channel ob * 32 + (v & 3) + 8 (v >> 2) + 4 h of row r
@@ -219,7 +181,7 @@ __device__ __forceinline__ void rpn_head_walk(long tiles, const float *__restric
 #pragma unroll
                             for (int e = 0; e < 4; ++e) {
                                 v4[e] = y[ob][4 * g + e] + b2s[o0 + e];
-                                if (relu2) v4[e] = heads_relu(v4[e]);
+                                if (relu2) v4[e] = relu_keep_nan(v4[e]);
                             }
                             if (o2 % 4 == 0) {
                                 *reinterpret_cast<float4 *>(orow + o0) = make_float4(v4[0], v4[1], v4[2], v4[3]);
@@ -260,18 +222,6 @@ __global__ __launch_bounds__(HEADS_THREADS) void rpn_heads_kernel(long tiles, co
         rpn_head_walk<NB2>(tiles, x, smem_heads, out_reg, ticket, next_chunk, chunk);
 }
 
-static int heads_cu_count() {
-    static int cus[64] = {0};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (cus[dev] == 0) {
-        int n = 0;
-        if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n <= 0) n = 256;
-        cus[dev] = n;
-    }
-    return cus[dev];
-}
-
 }  // namespace ws3d
 
 extern "C" size_t ws3d_rpn_heads_blob_bytes(int o2) {
@@ -309,7 +259,7 @@ extern "C" int ws3d_rpn_heads(long rows, const float *x_rows, int heads, const v
     if (rows == 0) return WS3D_OK;
     const long tiles = rows / 32, chunks = (tiles + 7) / 8;
     // the regression head's tile costs 288 bf16 MFMAs, the classification head's 192 + a dot product: 2 : 3 of the workgroups
-    const long wgs_all = workgroups > 0 ? workgroups : heads_cu_count();
+    const long wgs_all = workgroups > 0 ? workgroups : cu_count();
     long wg_cls = 0, wg_reg = 0;
     if (do_cls && do_reg) {
         wg_cls = std::max(1L, std::min(chunks, (wgs_all * 2 + 2) / 5));

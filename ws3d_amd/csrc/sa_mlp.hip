@@ -16,6 +16,7 @@
 
 #include "common.h"
 #include "compact_pool.h"
+#include "mfma_tile.h"
 
 namespace ws3d {
 
@@ -103,95 +104,135 @@ __global__ __launch_bounds__(256) void sa_mlp3_pool_kernel(long rows, const floa
 // Every layer is computed transposed, out^T = W^T X^T, with v_mfma_f32_32x32x2_f32: the A operand is W^T (lane l holds
 // W^T[o = l % 32][k]), the B operand X^T (lane l holds X[row = l % 32][k]; lanes 0-31 supply the first K element of a step,
 // lanes 32-63 the second), and the accumulator comes out as lane = row, register v (with the lane's half h = l / 32) = channel
-// kp(v, h) = 8 (v / 4) + 4 h + v % 4.  That is exactly the shape of the NEXT layer's B operand if step v of the next layer pairs
-// the K elements (kp(v, 0), kp(v, 1)) -- the order of the K steps is free as long as the A operand follows it -- so
+// acc_row(v, h) (mfma_tile.h).  That is exactly the shape of the NEXT layer's B operand if step v of the next layer pairs
+// the K elements (acc_row(v, 0), acc_row(v, 1)) -- the order of the K steps is free as long as the A operand follows it -- so
 // bias + ReLU are applied to the accumulator registers and they are fed straight back in: no shuffle, no LDS, no barrier
 // between the layers.  The weights live in registers (2 + 16 + 32 per lane, loaded once per wave), a wave walks over tiles of
-// 32 grouped rows (one centre at nsample 32, two at 16); the last layer is multiplied the other way round (same registers,
-// operands swapped) so that the pool runs over registers.
+// 32 rows; the last layer is multiplied the other way round (same registers, operands swapped) so that the pool runs over
+// registers.
 // 50 MFMAs per tile = 3,200 matrix-core cycles against ~6,500 VALU cycles of the kernel above (wide scale; the narrow one,
 // 16-16-32, uses half of the accumulator rows in layers 1 and 2: 18 MFMAs per tile).
-typedef float sa_f16 __attribute__((ext_vector_type(16)));
+//
+// The chain exists ONCE (Sa1Chain); a kernel is a row source + the chain + a pool:
+//   sa_mlp3_pool_mfma_kernel      rows of the grouped tensor               stored register pool
+//   sa_mlp3_compact_mfma_kernel   distinct (centre, sample) pairs, sa1_row  atomic pool (compact_pool.h)
+//   sa_mlp3_lists_mfma_kernel     all rows of the neighbour lists, sa1_row  stored register pool
+// so a row's activations are the same bits in all three, and the maximum is order-free.  ReLU and pool are fmaxf here (a NaN is
+// dropped; compact_pool.h says why this family differs from mfma_tile.h's pool_rows / bias_relu, which keep it).
+template <int C1, int C2, int C3>
+struct Sa1Chain {
+    static_assert((C1 == 16 || C1 == 32) && (C2 == 16 || C2 == 32) && (C3 == 32 || C3 == 64), "shape");
+    static constexpr int V1 = C1 / 2, V2 = C2 / 2, NB3 = C3 / 32;      // K steps of layers 2 / 3 (channel pairs), 32-channel blocks of layer 3
+    // a 16-channel layer fills half of the 32 accumulator rows: its weights beyond the width are zero, its K steps half as many
+    float a1[2], a2[V1], a3[NB3][V2], bb1[V1], bb2[V2], b3v[NB3];
 
+    // lane (c = lane % 32, h = lane / 32)
+    __device__ __forceinline__ Sa1Chain(const float *__restrict__ w1t, const float *__restrict__ b1, const float *__restrict__ w2t,
+                                        const float *__restrict__ b2, const float *__restrict__ w3t, const float *__restrict__ b3, int h, int c) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) a1[j] = c < C1 ? w1t[(2 * j + h) * C1 + c] : 0.f;
+#pragma unroll
+        for (int v = 0; v < V1; ++v) {
+            a2[v] = c < C2 ? w2t[acc_row(v, h) * C2 + c] : 0.f;
+            bb1[v] = b1[acc_row(v, h)];
+        }
+#pragma unroll
+        for (int v = 0; v < V2; ++v) {
+#pragma unroll
+            for (int blk = 0; blk < NB3; ++blk) a3[blk][v] = w3t[acc_row(v, h) * C3 + blk * 32 + c];
+            bb2[v] = b2[acc_row(v, h)];
+        }
+#pragma unroll
+        for (int blk = 0; blk < NB3; ++blk) b3v[blk] = b3[blk * 32 + c];
+    }
+
+    // layers 1 and 2 of this lane's row xr = [dx dy dz f] (both halves hold the whole row) -> the B operand of the last layer
+    __device__ __forceinline__ void layers12(float4 xr, int h, float (&act)[V2]) const {
+        const float x1[2] = {h ? xr.y : xr.x, h ? xr.w : xr.z};        // k = h, k = 2 + h
+        floatx16 acc;
+        acc_zero(acc);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[j], x1[j], acc, 0, 0, 0);
+        float act1[V1];
+#pragma unroll
+        for (int v = 0; v < V1; ++v) act1[v] = fmaxf(acc[v] + bb1[v], 0.f);
+        acc_zero(acc);
+#pragma unroll
+        for (int v = 0; v < V1; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[v], act1[v], acc, 0, 0, 0);
+#pragma unroll
+        for (int v = 0; v < V2; ++v) act[v] = fmaxf(acc[v] + bb2[v], 0.f);
+    }
+
+    // block blk of the LAST layer the other way round, out = X W (the very same registers, operands swapped): lane = channel
+    // blk * 32 + c, register v (+ half) = row acc_row(v, h) of the tile, before bias -- so the pool over the rows of a centre is a
+    // maximum over REGISTERS instead of five DPP stages for each of 16 registers
+    __device__ __forceinline__ floatx16 layer3(const float (&act)[V2], int blk) const {
+        floatx16 acc;
+        acc_zero(acc);
+#pragma unroll
+        for (int v = 0; v < V2; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(act[v], a3[blk][v], acc, 0, 0, 0);
+        return acc;
+    }
+};
+
+// the 4-channel input row [dx dy dz f] of (centre cm of all scenes' b * m, source point src of its scene) from xyz / new_xyz / the
+// one feature channel -- no grouped tensor.  (CM: the caller's index width, in which cm / m is divided.)
+template <class CM>
+__device__ __forceinline__ float4 sa1_row(int n, int m, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+                                          const float *__restrict__ feat, CM cm, int src) {
+    const size_t p = (size_t)(cm / m) * n + (size_t)src;
+    const float *pr = xyz + p * 3, *cr = new_xyz + (size_t)cm * 3;
+    return make_float4(pr[0] - cr[0], pr[1] - cr[1], pr[2] - cr[2], feat[p]);
+}
+
+// the STORED pool of a tile of 32 rows in list order (one centre at NS = 32, two at 16) over the registers of Sa1Chain::layer3:
+// rows 16 g .. 16 g + 15 are registers 8 g .. 8 g + 7 of the two halves of the wave, which exchange their maxima; bias and ReLU
+// follow the maximum (they commute with it exactly).  out_col = the output column of this lane in row 0.
+template <int NS>
+__device__ __forceinline__ void sa1_pool_store(const floatx16 &acc, float bias, int relu3, float *__restrict__ out_col, long tile, int out_stride,
+                                               int h) {
+    static_assert(NS == 16 || NS == 32, "nsample");
+    constexpr int G = 32 / NS, R = 16 / G;                   // centres of the tile, registers per centre
+    float mx[G];
+#pragma unroll
+    for (int g = 0; g < G; ++g) {
+        mx[g] = acc[R * g];
+#pragma unroll
+        for (int v = 1; v < R; ++v) mx[g] = fmaxf(mx[g], acc[R * g + v]);
+        mx[g] = fmaxf(mx[g], __shfl_xor(mx[g], 32));
+    }
+    float y = (G == 2 && h ? mx[G - 1] : mx[0]) + bias;       // two centres: half 0 writes the first, half 1 the second
+    if (relu3) y = fmaxf(y, 0.f);
+    if (G == 2 || h == 0) out_col[(tile * G + (G == 2 ? h : 0)) * (long)out_stride] = y;
+}
+
+// Waves per SIMD (= four-wave workgroups per CU) the two stored-pool kernels are allocated for: what they reached by themselves
+// with the chain written out in each (3 wide, 5-6 narrow).  Unstated, the allocator keeps the accumulators of two layers in
+// separate AGPRs and the narrow grouped kernel ends at 90 registers and five waves (profiles/chain_cores_refactor.txt).
+constexpr int sa1_stored_waves(int c3) { return c3 == 64 ? 3 : 6; }
+
+// ---- the chain over the rows of the grouped tensor x (tiles * 32 rows of 4 channels)
 template <int C1, int C2, int C3, int NS>
-__global__ __launch_bounds__(256) void sa_mlp3_pool_mfma_kernel(long tiles, const float *__restrict__ x, const float *__restrict__ w1t,
+__global__ __launch_bounds__(256, sa1_stored_waves(C3)) void sa_mlp3_pool_mfma_kernel(long tiles, const float *__restrict__ x, const float *__restrict__ w1t,
                                                                 const float *__restrict__ b1, const float *__restrict__ w2t,
                                                                 const float *__restrict__ b2, const float *__restrict__ w3t,
                                                                 const float *__restrict__ b3, int relu3, float *__restrict__ out,
                                                                 int out_stride) {
-    static_assert((NS == 16 || NS == 32) && (C1 == 16 || C1 == 32) && (C2 == 16 || C2 == 32) && (C3 == 32 || C3 == 64), "shape");
-    constexpr int V1 = C1 / 2, V2 = C2 / 2, NB3 = C3 / 32;      // K steps of layers 2 / 3 (channel pairs), 32-channel blocks of layer 3
+    typedef Sa1Chain<C1, C2, C3> Chain;
     const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-    auto kp = [&](int v) { return 8 * (v / 4) + 4 * h + (v % 4); };
-    // a 16-channel layer fills half of the 32 accumulator rows: its weights beyond the width are zero, its K steps half as many
-    float a1[2], a2[V1], a3[NB3][V2], bb1[V1], bb2[V2], b3v[NB3];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) a1[j] = c < C1 ? w1t[(2 * j + h) * C1 + c] : 0.f;
-#pragma unroll
-    for (int v = 0; v < V1; ++v) {
-        a2[v] = c < C2 ? w2t[kp(v) * C2 + c] : 0.f;
-        bb1[v] = b1[kp(v)];
-    }
-#pragma unroll
-    for (int v = 0; v < V2; ++v) {
-#pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) a3[blk][v] = w3t[kp(v) * C3 + blk * 32 + c];
-        bb2[v] = b2[kp(v)];
-    }
-#pragma unroll
-    for (int blk = 0; blk < NB3; ++blk) b3v[blk] = b3[blk * 32 + c];
+    const Chain chain(w1t, b1, w2t, b2, w3t, b3, h, c);
     const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
     for (long tile = wave; tile < tiles; tile += nwaves) {
-        const float4 xr = reinterpret_cast<const float4 *>(x)[tile * 32 + c];          // row c of the tile (both halves)
-        sa_f16 acc;
+        float act[Chain::V2];
+        chain.layers12(reinterpret_cast<const float4 *>(x)[tile * 32 + c], h, act);          // row c of the tile (both halves)
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0], h ? xr.y : xr.x, acc, 0, 0, 0);   // k = h
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1], h ? xr.w : xr.z, acc, 0, 0, 0);   // k = 2 + h
-        float act[16];
-#pragma unroll
-        for (int v = 0; v < V1; ++v) act[v] = fmaxf(acc[v] + bb1[v], 0.f);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-        for (int v = 0; v < V1; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[v], act[v], acc, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < V2; ++v) act[v] = fmaxf(acc[v] + bb2[v], 0.f);
-#pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-            // the LAST layer the other way round, out = X W (the very same registers, operands swapped): lane = channel,
-            // register v (+ half) = row kp(v, h) -- so the pool over the rows of a centre is a maximum over REGISTERS (15
-            // v_max + one exchange between the halves) instead of five DPP stages for each of 16 registers
-#pragma unroll
-            for (int v = 0; v < V2; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(act[v], a3[blk][v], acc, 0, 0, 0);
-            const float bias = b3v[blk];
-            if (NS == 32) {
-                float m = acc[0];
-#pragma unroll
-                for (int v = 1; v < 16; ++v) m = fmaxf(m, acc[v]);
-                m = fmaxf(m, __shfl_xor(m, 32));                     // rows 4h .. of the other half
-                m += bias;
-                if (relu3) m = fmaxf(m, 0.f);
-                if (h == 0) out[tile * (long)out_stride + blk * 32 + c] = m;
-            } else {
-                float m0 = acc[0], m1 = acc[8];                      // rows 0-15 (registers 0-7) / rows 16-31 (registers 8-15)
-#pragma unroll
-                for (int v = 1; v < 8; ++v) { m0 = fmaxf(m0, acc[v]); m1 = fmaxf(m1, acc[8 + v]); }
-                m0 = fmaxf(m0, __shfl_xor(m0, 32));
-                m1 = fmaxf(m1, __shfl_xor(m1, 32));
-                float m = (h ? m1 : m0) + bias;                      // half 0 writes the first centre, half 1 the second
-                if (relu3) m = fmaxf(m, 0.f);
-                out[(tile * 2 + h) * (long)out_stride + blk * 32 + c] = m;
-            }
-        }
+        for (int blk = 0; blk < Chain::NB3; ++blk)
+            sa1_pool_store<NS>(chain.layer3(act, blk), chain.b3v[blk], relu3, out + blk * 32 + c, tile, out_stride, h);
     }
 }
 
 // ---- the same chain over COMPACT (centre, sample) pairs (gemm_pool.hip: a ball-query list is mostly padding, a padded row
-// repeats row 0 of its centre and cannot change the maximum).  Row t = (centre rowc[t], source point rowsrc[t]); the 4-channel
-// input row [dx dy dz f] is built here from xyz / new_xyz / the one feature channel -- no grouped tensor -- and the pool is an
+// repeats row 0 of its centre and cannot change the maximum).  Row t = (centre rowc[t], source point rowsrc[t]), and the pool is an
 // integer atomic max of the ReLU'd values (>= 0) into the centre's row, which the caller zeroes.  *total rows; the grid is
 // sized for the worst case and waves walk the tiles that exist.
 #ifndef SA1_ABL
@@ -205,30 +246,13 @@ __global__ __launch_bounds__(256) void sa_mlp3_compact_mfma_kernel(int n, int m,
                                                                    const float *__restrict__ w2t, const float *__restrict__ b2,
                                                                    const float *__restrict__ w3t, const float *__restrict__ b3,
                                                                    float *__restrict__ out, int out_stride, long limit) {
-    static_assert((C1 == 16 || C1 == 32) && (C2 == 16 || C2 == 32) && (C3 == 32 || C3 == 64), "shape");
-    constexpr int V1 = C1 / 2, V2 = C2 / 2, NB3 = C3 / 32;
+    typedef Sa1Chain<C1, C2, C3> Chain;
     const long T = *total;
     const long tiles = (T + 31) / 32;
     const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
     if (wave >= tiles || (limit >= 0 && T > limit)) return;       // beyond the limit sa_mlp3_lists_mfma_kernel runs instead
     const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-    auto kp = [&](int v) { return 8 * (v / 4) + 4 * h + (v % 4); };
-    float a1[2], a2[V1], a3[NB3][V2], bb1[V1], bb2[V2], b3v[NB3];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) a1[j] = c < C1 ? w1t[(2 * j + h) * C1 + c] : 0.f;
-#pragma unroll
-    for (int v = 0; v < V1; ++v) {
-        a2[v] = c < C2 ? w2t[kp(v) * C2 + c] : 0.f;
-        bb1[v] = b1[kp(v)];
-    }
-#pragma unroll
-    for (int v = 0; v < V2; ++v) {
-#pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) a3[blk][v] = w3t[kp(v) * C3 + blk * 32 + c];
-        bb2[v] = b2[kp(v)];
-    }
-#pragma unroll
-    for (int blk = 0; blk < NB3; ++blk) b3v[blk] = b3[blk * 32 + c];
+    const Chain chain(w1t, b1, w2t, b2, w3t, b3, h, c);
     // the row of a tile is two dependent round trips away (compact row -> (centre, source point) -> coordinates): the indices are
     // fetched two tiles ahead and the coordinates one tile ahead, under the matrix chain of the tile in hand
     auto row_index = [&](long tile, int &cm, int &src) {
@@ -236,14 +260,9 @@ __global__ __launch_bounds__(256) void sa_mlp3_compact_mfma_kernel(int n, int m,
         cm = rowc[t];
         src = rowsrc[t];
     };
-    auto row_fetch = [&](int cm, int src) {
-        const size_t p = (size_t)(cm / m) * n + (size_t)src;
-        const float *pr = xyz + p * 3, *cr = new_xyz + (size_t)cm * 3;
-        return make_float4(pr[0] - cr[0], pr[1] - cr[1], pr[2] - cr[2], feat[p]);
-    };
     int cm_n, src_n;
     row_index(wave, cm_n, src_n);
-    float4 xr_n = row_fetch(cm_n, src_n);
+    float4 xr_n = sa1_row(n, m, xyz, new_xyz, feat, cm_n, src_n);
     row_index(wave + nwaves, cm_n, src_n);
     for (long tile = wave; tile < tiles; tile += nwaves) {
         float4 xr = xr_n;
@@ -251,24 +270,12 @@ __global__ __launch_bounds__(256) void sa_mlp3_compact_mfma_kernel(int n, int m,
         xr = make_float4((float)c, (float)(tile & 255), 1.f, 0.5f);
 #else
         if (tile + nwaves < tiles) {
-            xr_n = row_fetch(cm_n, src_n);
+            xr_n = sa1_row(n, m, xyz, new_xyz, feat, cm_n, src_n);
             row_index(tile + 2 * nwaves, cm_n, src_n);
         }
 #endif
-        sa_f16 acc;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0], h ? xr.y : xr.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1], h ? xr.w : xr.z, acc, 0, 0, 0);
-        float act[16];
-#pragma unroll
-        for (int v = 0; v < V1; ++v) act[v] = fmaxf(acc[v] + bb1[v], 0.f);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-        for (int v = 0; v < V1; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[v], act[v], acc, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < V2; ++v) act[v] = fmaxf(acc[v] + bb2[v], 0.f);
+        float act[Chain::V2];
+        chain.layers12(xr, h, act);
         // the centres of the 16 consecutive rows this half pools (compact_pool.h), once for all channel blocks
         int cen[16];
 #if SA1_ABL & 2
@@ -278,12 +285,9 @@ __global__ __launch_bounds__(256) void sa_mlp3_compact_mfma_kernel(int n, int m,
         compact_centres16(rowc, tile * 32 + 16 * h, T, cen);
 #endif
 #pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int v = 0; v < V2; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(act[v], a3[blk][v], acc, 0, 0, 0);
-            const float bias = b3v[blk];
+        for (int blk = 0; blk < Chain::NB3; ++blk) {
+            const floatx16 acc = chain.layer3(act, blk);
+            const float bias = chain.b3v[blk];
 #if SA1_ABL & 1     // (what the atomic epilogue costs: one plain store per tile and block instead)
             float mx = 0.f;
 #pragma unroll
@@ -297,90 +301,30 @@ __global__ __launch_bounds__(256) void sa_mlp3_compact_mfma_kernel(int n, int m,
 }
 
 // ---- the same chain over ALL rows of the neighbour lists, without a grouped tensor: row r = (centre r / NS, source point
-// nbr[r]) is built here like in the compact kernel, the pool runs over registers like in sa_mlp3_pool_mfma_kernel (a tile of 32
-// rows holds one centre at NS = 32, two at 16) and is STORED -- no atomics, no zeroed output.  This is the dense side of the
+// nbr[r]), the pool is STORED -- no atomics, no zeroed output.  This is the dense side of the
 // device-side dispatch: launched next to the compact kernel with a gate on the pair total (run iff *gate > gate_limit; a null
 // gate always runs), it replaces ws3d_query_and_group_nlc + ws3d_sa_mlp3_pool (25 MB of grouped rows written and read back per
-// batch of 8 scenes).  Bit-identical to both: a row's activations are its own, the maximum is order-free.
+// batch of 8 scenes).  Bit-identical to both.
 template <int C1, int C2, int C3, int NS>
-__global__ __launch_bounds__(256) void sa_mlp3_lists_mfma_kernel(long tiles, int n, int m, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
+__global__ __launch_bounds__(256, sa1_stored_waves(C3)) void sa_mlp3_lists_mfma_kernel(long tiles, int n, int m, const float *__restrict__ xyz, const float *__restrict__ new_xyz,
                                                                  const float *__restrict__ feat, const int32_t *__restrict__ nbr,
                                                                  const float *__restrict__ w1t, const float *__restrict__ b1,
                                                                  const float *__restrict__ w2t, const float *__restrict__ b2,
                                                                  const float *__restrict__ w3t, const float *__restrict__ b3, int relu3,
                                                                  float *__restrict__ out, int out_stride, const int32_t *__restrict__ gate,
                                                                  long gate_limit) {
-    static_assert((NS == 16 || NS == 32) && (C1 == 16 || C1 == 32) && (C2 == 16 || C2 == 32) && (C3 == 32 || C3 == 64), "shape");
+    typedef Sa1Chain<C1, C2, C3> Chain;
     if (gate && (long)*gate <= gate_limit) return;
-    constexpr int V1 = C1 / 2, V2 = C2 / 2, NB3 = C3 / 32;
     const int lane = threadIdx.x & 63, h = lane >> 5, c = lane & 31;
-    auto kp = [&](int v) { return 8 * (v / 4) + 4 * h + (v % 4); };
-    float a1[2], a2[V1], a3[NB3][V2], bb1[V1], bb2[V2], b3v[NB3];
-#pragma unroll
-    for (int j = 0; j < 2; ++j) a1[j] = c < C1 ? w1t[(2 * j + h) * C1 + c] : 0.f;
-#pragma unroll
-    for (int v = 0; v < V1; ++v) {
-        a2[v] = c < C2 ? w2t[kp(v) * C2 + c] : 0.f;
-        bb1[v] = b1[kp(v)];
-    }
-#pragma unroll
-    for (int v = 0; v < V2; ++v) {
-#pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) a3[blk][v] = w3t[kp(v) * C3 + blk * 32 + c];
-        bb2[v] = b2[kp(v)];
-    }
-#pragma unroll
-    for (int blk = 0; blk < NB3; ++blk) b3v[blk] = b3[blk * 32 + c];
+    const Chain chain(w1t, b1, w2t, b2, w3t, b3, h, c);
     const long wave = (long)blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = (long)gridDim.x * 4;
     for (long tile = wave; tile < tiles; tile += nwaves) {
-        float4 xr;
-        {
-            const long r = tile * 32 + c;
-            const long cm = r / NS;
-            const size_t p = (size_t)(cm / m) * n + (size_t)nbr[r];
-            const float *pr = xyz + p * 3, *cr = new_xyz + (size_t)cm * 3;
-            xr = make_float4(pr[0] - cr[0], pr[1] - cr[1], pr[2] - cr[2], feat[p]);
-        }
-        sa_f16 acc;
+        const long r = tile * 32 + c;
+        float act[Chain::V2];
+        chain.layers12(sa1_row(n, m, xyz, new_xyz, feat, r / NS, nbr[r]), h, act);
 #pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[0], h ? xr.y : xr.x, acc, 0, 0, 0);
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a1[1], h ? xr.w : xr.z, acc, 0, 0, 0);
-        float act[16];
-#pragma unroll
-        for (int v = 0; v < V1; ++v) act[v] = fmaxf(acc[v] + bb1[v], 0.f);
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-        for (int v = 0; v < V1; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a2[v], act[v], acc, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < V2; ++v) act[v] = fmaxf(acc[v] + bb2[v], 0.f);
-#pragma unroll
-        for (int blk = 0; blk < NB3; ++blk) {
-#pragma unroll
-            for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-#pragma unroll
-            for (int v = 0; v < V2; ++v) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(act[v], a3[blk][v], acc, 0, 0, 0);
-            const float bias = b3v[blk];
-            if (NS == 32) {
-                float mx = acc[0];
-#pragma unroll
-                for (int v = 1; v < 16; ++v) mx = fmaxf(mx, acc[v]);
-                mx = fmaxf(mx, __shfl_xor(mx, 32));
-                mx += bias;
-                if (relu3) mx = fmaxf(mx, 0.f);
-                if (h == 0) out[tile * (long)out_stride + blk * 32 + c] = mx;
-            } else {
-                float m0 = acc[0], m1 = acc[8];
-#pragma unroll
-                for (int v = 1; v < 8; ++v) { m0 = fmaxf(m0, acc[v]); m1 = fmaxf(m1, acc[8 + v]); }
-                m0 = fmaxf(m0, __shfl_xor(m0, 32));
-                m1 = fmaxf(m1, __shfl_xor(m1, 32));
-                float mx = (h ? m1 : m0) + bias;
-                if (relu3) mx = fmaxf(mx, 0.f);
-                out[(tile * 2 + h) * (long)out_stride + blk * 32 + c] = mx;
-            }
-        }
+        for (int blk = 0; blk < Chain::NB3; ++blk)
+            sa1_pool_store<NS>(chain.layer3(act, blk), chain.b3v[blk], relu3, out + blk * 32 + c, tile, out_stride, h);
     }
 }
 
@@ -415,7 +359,6 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
     }
     if (tid < 128) b1s[tid] = b1 ? b1[tid] : 0.f;
     __syncthreads();
-    auto kp = [&](int v) { return 8 * (v / 4) + 4 * h + (v % 4); };
     const float *wbase = w1s + 64 * h * 128 + c + 32 * h;       // column block blk of this half's rows sits at (blk ^ h) * 32
     // (prefetching the next tile's rows into 64 more registers was measured: 60 vs 54 us at 131072 rows x (128 -> 128 -> 1))
     // chunks of 8 tiles (one per wave) are handed out by a ticket counter when the caller provides one (zero on entry): with a
@@ -435,7 +378,7 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
             const float4 t = xp[q];
             xv[4 * q] = t.x; xv[4 * q + 1] = t.y; xv[4 * q + 2] = t.z; xv[4 * q + 3] = t.w;
         }
-        sa_f16 acc[4];
+        floatx16 acc[4];
 #pragma unroll
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
@@ -451,12 +394,12 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
         for (int blk = 0; blk < 4; ++blk)
 #pragma unroll
             for (int v = 0; v < 16; ++v) {
-                float y = acc[blk][v] + b1s[blk * 32 + kp(v)];
+                float y = acc[blk][v] + b1s[blk * 32 + acc_row(v, h)];
                 acc[blk][v] = relu1 ? fmaxf(y, 0.f) : y;
             }
 #pragma unroll
         for (int blk2 = 0; blk2 < O2B; ++blk2) {
-            sa_f16 acc2;
+            floatx16 acc2;
 #pragma unroll
             for (int i = 0; i < 16; ++i) acc2[i] = 0.f;
 #pragma unroll
@@ -464,7 +407,7 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
 #pragma unroll
                 for (int v = 0; v < 16; ++v)
                 {
-                    acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[blk][v], w2s[(blk * 32 + kp(v)) * W2S + blk2 * 32 + c], acc2, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_f32_32x32x2f32(acc[blk][v], w2s[(blk * 32 + acc_row(v, h)) * W2S + blk2 * 32 + c], acc2, 0, 0, 0);
                     if ((v & 7) == 7) __builtin_amdgcn_sched_barrier(0);
                 }
             const int col = blk2 * 32 + c;
@@ -475,7 +418,7 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
                 for (int v = 0; v < 16; ++v) {
                     float y = acc2[v] + bv;
                     if (relu2) y = fmaxf(y, 0.f);
-                    o[(long)(8 * (v / 4) + (v % 4)) * o2] = y;
+                    o[(long)acc_row(v, 0) * o2] = y;
                 }
             }
         }
@@ -488,6 +431,33 @@ __global__ __launch_bounds__(512) void mlp2_rows_kernel(long tiles, int o2, cons
             chunk += gridDim.x;
         }
     }
+}
+
+// the width sets SA1's kernels are built for -> f(Sa1Shape<C1, C2, C3>()); with an nsample of 16 | 32 -> f(Sa1Shape<C1, C2, C3, NS>());
+// false: none (nothing called)
+template <int A, int B, int C, int N = 0> struct Sa1Shape { static constexpr int c1 = A, c2 = B, c3 = C, ns = N; };
+template <class F>
+static bool sa1_widths(int c1, int c2, int c3, F f) {
+    if (c1 == 32 && c2 == 32 && c3 == 64) { f(Sa1Shape<32, 32, 64>()); return true; }
+    if (c1 == 16 && c2 == 16 && c3 == 32) { f(Sa1Shape<16, 16, 32>()); return true; }
+    return false;
+}
+template <class F>
+static bool sa1_shapes(int c1, int c2, int c3, int nsample, F f) {
+    if (nsample != 16 && nsample != 32) return false;
+    return sa1_widths(c1, c2, c3, [&](auto w) {
+        typedef decltype(w) W;
+        if (nsample == 16) f(Sa1Shape<W::c1, W::c2, W::c3, 16>());
+        else f(Sa1Shape<W::c1, W::c2, W::c3, 32>());
+    });
+}
+
+// workgroups of the three matrix-core chains: four waves each, which walk over the tiles; 3 workgroups per CU unless ws3d_tune key 2
+// says otherwise (a caller with many batches in flight asks for 192: +2 % on the 20-deep c3 step, profiles/r06_tune_workgroups.txt --
+// ws3d_amd/pipeline.py)
+static unsigned sa1_grid(long tiles) {
+    const long cap = g_tune[TUNE_SA1_WGS] > 0 ? g_tune[TUNE_SA1_WGS] : 768;
+    return (unsigned)(tiles / 4 < cap ? (tiles + 3) / 4 : cap);
 }
 
 }  // namespace ws3d
@@ -507,34 +477,17 @@ extern "C" int ws3d_sa_mlp3_pool(long rows, int nsample, int c1, int c2, int c3,
     const long blocks = (rows + 255) / 256;
     if (blocks > 0x7fffffffL) { set_error("ws3d_sa_mlp3_pool: too many rows"); return WS3D_E_UNSUPPORTED; }
     hipStream_t st = as_stream(stream);
-    // on the matrix cores when the rows fill whole 32-row tiles (the VALU kernel below serves the ragged shapes)
-    if (rows % 32 == 0) {
-        const long tiles = rows / 32;
-        const long cap1 = g_tune[TUNE_SA1_WGS] > 0 ? g_tune[TUNE_SA1_WGS] : 768;          // (ws3d_tune key 2)
-    const unsigned grid = (unsigned)(tiles / 4 < cap1 ? (tiles + 3) / 4 : cap1);          // 3 workgroups per CU, waves walk over tiles
-#define WS3D_SA_MFMA_CASE(A, B, C, N)                                                                                     \
-        if (c1 == A && c2 == B && c3 == C && nsample == N) {                                                              \
-            hipLaunchKernelGGL((sa_mlp3_pool_mfma_kernel<A, B, C, N>), dim3(grid), dim3(256), 0, st, tiles, x_rows4, w1t, b1, w2t, b2, \
-                               w3t, b3, relu3, out, out_stride);                                                          \
-            return check_launch("ws3d_sa_mlp3_pool");                                                                     \
-        }
-        WS3D_SA_MFMA_CASE(32, 32, 64, 32)
-        WS3D_SA_MFMA_CASE(32, 32, 64, 16)
-        WS3D_SA_MFMA_CASE(16, 16, 32, 16)
-        WS3D_SA_MFMA_CASE(16, 16, 32, 32)
-#undef WS3D_SA_MFMA_CASE
-    }
-#define WS3D_SA_MLP(A, B, C, N)                                                                                          \
-    if (c1 == A && c2 == B && c3 == C && nsample == N) {                                                                 \
-        hipLaunchKernelGGL((sa_mlp3_pool_kernel<A, B, C, N>), dim3((unsigned)blocks), dim3(256), 0, st, rows, x_rows4,   \
-                           w1t, b1, w2t, b2, w3t, b3, relu3, out, out_stride);                                           \
-        return check_launch("ws3d_sa_mlp3_pool");                                                                        \
-    }
-    WS3D_SA_MLP(16, 16, 32, 16)
-    WS3D_SA_MLP(32, 32, 64, 32)
-    WS3D_SA_MLP(16, 16, 32, 32)
-    WS3D_SA_MLP(32, 32, 64, 16)
-#undef WS3D_SA_MLP
+    // on the matrix cores when the rows fill whole 32-row tiles, else the VALU kernel (it serves the ragged shapes)
+    const bool ok = sa1_shapes(c1, c2, c3, nsample, [&](auto s) {
+        typedef decltype(s) S;
+        if (rows % 32 == 0)
+            hipLaunchKernelGGL((sa_mlp3_pool_mfma_kernel<S::c1, S::c2, S::c3, S::ns>), dim3(sa1_grid(rows / 32)), dim3(256), 0, st, rows / 32, x_rows4, w1t,
+                               b1, w2t, b2, w3t, b3, relu3, out, out_stride);
+        else
+            hipLaunchKernelGGL((sa_mlp3_pool_kernel<S::c1, S::c2, S::c3, S::ns>), dim3((unsigned)blocks), dim3(256), 0, st, rows, x_rows4, w1t, b1, w2t,
+                               b2, w3t, b3, relu3, out, out_stride);
+    });
+    if (ok) return check_launch("ws3d_sa_mlp3_pool");
     set_error("ws3d_sa_mlp3_pool: no kernel for widths (%d, %d, %d) x nsample %d", c1, c2, c3, nsample);
     return WS3D_E_UNSUPPORTED;
 }
@@ -573,19 +526,12 @@ extern "C" int ws3d_sa_mlp3_pool_compact(int b, int n, int m, long max_rows, int
         return WS3D_E_INVALID;
     }
     const long tiles = (max_rows + 31) / 32;
-    // 3 workgroups per CU, waves walk over tiles; ws3d_tune key 2 (a caller with many batches in flight asks for 192: +2 % on the
-    // 20-deep c3 step, profiles/r06_tune_workgroups.txt -- ws3d_amd/pipeline.py)
-    const long cap1 = g_tune[TUNE_SA1_WGS] > 0 ? g_tune[TUNE_SA1_WGS] : 768;
-    const unsigned grid = (unsigned)(tiles / 4 < cap1 ? (tiles + 3) / 4 : cap1);
-#define WS3D_SA_COMPACT(A, B, C)                                                                                                        \
-    if (c1 == A && c2 == B && c3 == C) {                                                                                                \
-        hipLaunchKernelGGL((sa_mlp3_compact_mfma_kernel<A, B, C>), dim3(grid), dim3(256), 0, as_stream(stream), n, m, xyz, new_xyz, feat, rowc, \
-                           rowsrc, total, w1t, b1, w2t, b2, w3t, b3, out, out_stride, limit);                                           \
-        return check_launch("ws3d_sa_mlp3_pool_compact");                                                                               \
-    }
-    WS3D_SA_COMPACT(32, 32, 64)
-    WS3D_SA_COMPACT(16, 16, 32)
-#undef WS3D_SA_COMPACT
+    const bool ok = sa1_widths(c1, c2, c3, [&](auto s) {
+        typedef decltype(s) S;
+        hipLaunchKernelGGL((sa_mlp3_compact_mfma_kernel<S::c1, S::c2, S::c3>), dim3(sa1_grid(tiles)), dim3(256), 0, as_stream(stream), n, m, xyz, new_xyz,
+                           feat, rowc, rowsrc, total, w1t, b1, w2t, b2, w3t, b3, out, out_stride, limit);
+    });
+    if (ok) return check_launch("ws3d_sa_mlp3_pool_compact");
     set_error("ws3d_sa_mlp3_pool_compact: no kernel for widths (%d, %d, %d)", c1, c2, c3);
     return WS3D_E_UNSUPPORTED;
 }
@@ -602,19 +548,12 @@ extern "C" int ws3d_sa_mlp3_pool_lists(int b, int n, int m, int nsample, int c1,
         return WS3D_E_INVALID;
     }
     const long tiles = rows / 32;
-    const long cap1 = g_tune[TUNE_SA1_WGS] > 0 ? g_tune[TUNE_SA1_WGS] : 768;          // (ws3d_tune key 2)
-    const unsigned grid = (unsigned)(tiles / 4 < cap1 ? (tiles + 3) / 4 : cap1);
-#define WS3D_SA_LISTS(A, B, C, N)                                                                                                       \
-    if (c1 == A && c2 == B && c3 == C && nsample == N) {                                                                                \
-        hipLaunchKernelGGL((sa_mlp3_lists_mfma_kernel<A, B, C, N>), dim3(grid), dim3(256), 0, as_stream(stream), tiles, n, m, xyz, new_xyz, feat, nbr, \
-                           w1t, b1, w2t, b2, w3t, b3, relu3, out, out_stride, gate, gate_limit);                                        \
-        return check_launch("ws3d_sa_mlp3_pool_lists");                                                                                 \
-    }
-    WS3D_SA_LISTS(32, 32, 64, 32)
-    WS3D_SA_LISTS(16, 16, 32, 16)
-    WS3D_SA_LISTS(32, 32, 64, 16)
-    WS3D_SA_LISTS(16, 16, 32, 32)
-#undef WS3D_SA_LISTS
+    const bool ok = sa1_shapes(c1, c2, c3, nsample, [&](auto s) {
+        typedef decltype(s) S;
+        hipLaunchKernelGGL((sa_mlp3_lists_mfma_kernel<S::c1, S::c2, S::c3, S::ns>), dim3(sa1_grid(tiles)), dim3(256), 0, as_stream(stream), tiles, n, m, xyz,
+                           new_xyz, feat, nbr, w1t, b1, w2t, b2, w3t, b3, relu3, out, out_stride, gate, gate_limit);
+    });
+    if (ok) return check_launch("ws3d_sa_mlp3_pool_lists");
     set_error("ws3d_sa_mlp3_pool_lists: no kernel for widths (%d, %d, %d) x nsample %d", c1, c2, c3, nsample);
     return WS3D_E_UNSUPPORTED;
 }
