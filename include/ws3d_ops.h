@@ -802,6 +802,33 @@ WS3D_API int ws3d_stage2_ioun_loss(int rows, const float *rcnn_iou, const float 
                                    const float *gt_boxes, const float *cls, float *vals, int32_t *counts, float *grad_iou, float *grad_ref,
                                    ws3d_stream_t stream);
 
+/* The Stage-1 training targets for a padded batch: generate_gaussian_training_labels (lib/datasets/kitti_rcnn_dataset.py:529-573), which
+ * the reference runs per scene on the host.  pts (batch, n, >= 3) with pts_stride floats from one point to the next (x, y, z lead),
+ * centres (batch, kmax, 3), count (batch) int32: the first count[b] centres of scene b are real, the others are never read (a count
+ * outside 0..kmax is clamped) -> cls_label (batch, n) = exp(-0.5 near^2 / gauss_cov) with near = clip(min_k d_k - gauss_status, 0, 100),
+ * d_k = sqrt(((px - cx)^2 + (py * gauss_height)^2) + (pz - cz)^2) in correctly rounded fp32 operations, the exponential in float64 and
+ * rounded once (labels beyond ~17 m are fp32 denormals, kept: they count as foreground); reg_label (batch, n, 3) = (cx - px, 0, cz - pz)
+ * of the FIRST nearest centre where d < 4, zeros elsewhere.  count[b] == 0: zeros.  One launch, no workspace.                          */
+WS3D_API int ws3d_rpn_center_labels(int batch, int n, int kmax, int pts_stride, float gauss_height, float gauss_status, double gauss_cov,
+                                    const float *pts, const float *centres, const int32_t *count, float *cls_label, float *reg_label,
+                                    ws3d_stream_t stream);
+/* The Stage-1 loss, get_rpn_loss (lib/net/train_functions.py:163-228) with SigmoidFocalClassificationLoss on soft targets and
+ * get_rpn_reg_loss (lib/utils/loss_utils.py:25-156), value AND gradient, no host branch on fg_sum and no read-back.
+ * rpn_cls (rows), rpn_reg (rows, 4 bins) laid out [x_bin | z_bin | x_res | z_res], cls_label (rows), reg_label (rows, 3) ->
+ *   vals (9) = rpn_loss = weight_cls * rpn_loss_cls + weight_reg * rpn_loss_reg, rpn_loss_cls, rpn_loss_reg = (x_bin + z_bin) + (x_res +
+ *              z_res), rpn_loss_cls_pos, rpn_loss_cls_neg, loss_x_bin, loss_z_bin, loss_x_res, loss_z_res
+ *   counts (1) int32 = foreground rows (cls_label > 0)
+ *   grad_cls (rows), grad_reg (rows, 4 bins) = d rpn_loss / d rpn_cls, d rpn_reg, written in full (zeros on the other rows).
+ * The focal weights are 1 / max(sum cls_label, 1); the regression terms are means over the foreground rows, sum / max(count, 1): no
+ * foreground row gives an exact 0.  Row terms in float64 from the fp32 inputs, float64 sums in a fixed order over per-workgroup
+ * partials, no atomics: a call is bit-reproducible and the workspace (ws3d_rpn_loss_workspace_bytes(rows), 8-byte aligned) carries
+ * nothing from call to call.  bins in 1..32; rpn_reg and grad_reg 16-byte aligned.  Three launches on `stream`.                       */
+WS3D_API size_t ws3d_rpn_loss_workspace_bytes(int rows);
+WS3D_API int ws3d_rpn_loss(int rows, int bins, double loc_scope, double loc_bin_size, double alpha, double gamma, double weight_cls,
+                           double weight_reg, const float *rpn_cls, const float *rpn_reg, const float *cls_label, const float *reg_label,
+                           float *vals, int32_t *counts, float *grad_cls, float *grad_reg, void *workspace, size_t workspace_bytes,
+                           ws3d_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -146,6 +146,9 @@ SIGNATURES = {
     "ws3d_stage2_select": (_i, [_i, _i, _f, _f, C.POINTER(_f), _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_stage2_rcnn_loss": (_i, [_i, _i, _i, _f, _f, _f, _f] + [_vp] * 9 + [_vp]),
     "ws3d_stage2_ioun_loss": (_i, [_i] + [_vp] * 10 + [_vp]),
+    "ws3d_rpn_center_labels": (_i, [_i, _i, _i, _i, _f, _f, C.c_double] + [_vp] * 5 + [_vp]),
+    "ws3d_rpn_loss_workspace_bytes": (_sz, [_i]),
+    "ws3d_rpn_loss": (_i, [_i, _i] + [C.c_double] * 6 + [_vp] * 8 + [_vp, _sz, _vp]),
 }
 
 

@@ -1684,6 +1684,70 @@ def stage2_ioun_loss(rcnn_iou, rcnn_ref, pred_boxes3d, refined_box, gt_boxes, cl
     return vals, counts, g_iou, g_ref
 
 
+def rpn_center_labels(pts, centres, count, gauss_height=0.707, gauss_status=0.7, gauss_cov=1.5, out=None):
+    """pts (B,N,C>=3) float32 (x, y, z lead; the last dimension contiguous, rows and scenes densely packed), centres (B,Kmax,3), count (B,)
+    int32 -> (cls_label (B,N), reg_label (B,N,3)) float32 as ws3d_rpn_center_labels lays them out: losses.gaussian_center_labels scene by
+    scene, the centres past count[b] never read.  out: the caller's (cls_label, reg_label).  No host synchronisation."""
+    dev = _dev(pts, centres, count)
+    _f32(pts, "pts"); _f32(centres, "centres")
+    if count.dtype != torch.int32:
+        raise Ws3dError(f"count must be int32, got {count.dtype}")
+    if pts.dim() != 3 or pts.size(2) < 3 or centres.dim() != 3 or centres.size(0) != pts.size(0) or centres.size(2) != 3 or tuple(count.shape) != (pts.size(0),):
+        raise ValueError("rpn_center_labels: shapes must be (B,N,C>=3) (B,Kmax,3) (B,)")
+    B, N, C = pts.shape
+    if out is None:
+        cls_label = torch.empty((B, N), dtype=torch.float32, device=dev)
+        reg_label = torch.empty((B, N, 3), dtype=torch.float32, device=dev)
+    else:
+        cls_label, reg_label = out
+        _dev(cls_label, reg_label)
+        if tuple(cls_label.shape) != (B, N) or tuple(reg_label.shape) != (B, N, 3) or cls_label.dtype != torch.float32 or reg_label.dtype != torch.float32:
+            raise ValueError("rpn_center_labels: out must be float32 (%d,%d) and (%d,%d,3)" % (B, N, B, N))
+    with _on(dev):
+        check(_lib.load().ws3d_rpn_center_labels(B, N, centres.size(1), C, float(gauss_height), float(gauss_status), float(gauss_cov), _p(pts),
+                                                 _p(centres), _p(count), _p(cls_label), _p(reg_label), _stream()), "rpn_center_labels")
+    return cls_label, reg_label
+
+
+def rpn_loss(rpn_cls, rpn_reg, cls_label, reg_label, loc_scope, loc_bin_size, alpha=0.25, gamma=2.0, loss_weight=(1.0, 1.0), out=None,
+             workspace=None):
+    """rpn_cls (R,), rpn_reg (R, 4*bins), cls_label (R,), reg_label (R,3), float32 ->
+    (vals (9,), counts (1,) int32, grad_cls (R,), grad_reg (R, 4*bins)) as ws3d_rpn_loss lays them out; no host synchronisation.
+    out: the caller's tuple of the same layout (grad_reg 16-byte aligned); workspace: a uint8 tensor of at least
+    ws3d_rpn_loss_workspace_bytes(R) bytes to reuse (nothing in it outlives a call)."""
+    dev = _dev(rpn_cls, rpn_reg, cls_label, reg_label)
+    for t, name in ((rpn_cls, "rpn_cls"), (rpn_reg, "rpn_reg"), (cls_label, "cls_label"), (reg_label, "reg_label")):
+        _f32(t, name)
+    bins = int((loc_scope + 1e-3) / loc_bin_size) * 2           # loss_utils.py:103, the expression of losses.rpn_reg_loss
+    R = rpn_cls.size(0)
+    if tuple(rpn_cls.shape) != (R,) or tuple(rpn_reg.shape) != (R, 4 * bins) or tuple(cls_label.shape) != (R,) or tuple(reg_label.shape) != (R, 3):
+        raise ValueError("rpn_loss: shapes must be (R,) (R,%d) (R,) (R,3)" % (4 * bins))
+    shapes = [(R,), (R, 4 * bins)]
+    if out is None:
+        vals, counts = torch.empty((9,), dtype=torch.float32, device=dev), torch.empty((1,), dtype=torch.int32, device=dev)
+        g_cls, g_reg = (torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes)
+    else:
+        want = [((9,), torch.float32), ((1,), torch.int32)] + [(sh, torch.float32) for sh in shapes]
+        if len(out) != len(want) or any(tuple(t.shape) != sh or t.dtype != dt for t, (sh, dt) in zip(out, want)):
+            raise ValueError("rpn_loss outputs must be %s" % (want,))
+        _dev(*out)
+        vals, counts, g_cls, g_reg = out
+    if R == 0:          # nothing to launch: every term is a sum over no row
+        vals.zero_(); counts.zero_()
+        return vals, counts, g_cls, g_reg
+    lib = _lib.load()
+    need = lib.ws3d_rpn_loss_workspace_bytes(R)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=dev)
+    elif workspace.dtype != torch.uint8 or workspace.numel() < need or _dev(workspace) != dev:
+        raise ValueError("rpn_loss: workspace must be a uint8 tensor of at least %d bytes on %s" % (need, dev))
+    with _on(dev):
+        check(lib.ws3d_rpn_loss(R, bins, float(loc_scope), float(loc_bin_size), float(alpha), float(gamma), float(loss_weight[0]),
+                                float(loss_weight[1]), _p(rpn_cls), _p(rpn_reg), _p(cls_label), _p(reg_label), _p(vals), _p(counts), _p(g_cls),
+                                _p(g_reg), _p(workspace), workspace.numel(), _stream()), "rpn_loss")
+    return vals, counts, g_cls, g_reg
+
+
 def _default_device():
     if not torch.cuda.is_available():
         raise Ws3dError("no HIP device: the reference's *_cpu entry points are served by the MI355X "

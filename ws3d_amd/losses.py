@@ -6,8 +6,11 @@
   * ``sigmoid_focal_loss``      -- SigmoidFocalClassificationLoss (lib/utils/loss_utils.py:25-90)
   * ``rpn_reg_loss``            -- get_rpn_reg_loss, bin classification + residual (:93-156)
   * ``rpn_loss``                -- get_rpn_loss (lib/net/train_functions.py:163-228), focal branch
-Everything here is plain torch / numpy: the custom kernels enter through the network's forward
-and (deterministic) backward.
+These are plain torch / numpy: the custom kernels enter through the network's forward and
+(deterministic) backward.  Opt-in, the same targets and loss from the device (csrc/rpn_targets.hip):
+  * ``center_labels_batch``     -- ``gaussian_center_labels`` for a padded batch, one HIP launch
+  * ``rpn_loss_fused``          -- ``rpn_loss(gaussian_center=True, lazy=True)``, value and gradient from
+    fused HIP with no boolean-mask indexing and no read-back of the foreground count
 """
 from __future__ import annotations
 
@@ -149,6 +152,59 @@ def rpn_loss(rpn_cls: torch.Tensor, rpn_reg: torch.Tensor, cls_label: torch.Tens
         loss_reg = loss_cls * 0
     loss = loss_cls * loss_weight[0] + loss_reg * loss_weight[1]
     tb.update({"rpn_loss_cls": read(loss_cls), "rpn_loss_reg": read(loss_reg), "rpn_loss": read(loss), "rpn_fg_sum": fg_sum})
+    return loss, tb
+
+
+def center_labels_batch(pts, centres, count, gauss_height: float = GAUSS_HEIGHT, gauss_status: float = GAUSS_STATUS,
+                        gauss_cov: float = GAUSS_COV):
+    """``gaussian_center_labels`` for a padded batch: pts (B,N,C>=3), centres (B,Kmax,3), count (B,) -- scene b has count[b] centres,
+    the padding behind them is ignored -> (cls_label (B,N), reg_label (B,N,3)) float32 tensors on pts' device.
+    float32 GPU tensors: one HIP launch (``ws3d_rpn_center_labels``), nothing read back.  Anything else: the numpy function, scene by
+    scene.  The two agree bit for bit on reg_label and on which labels are > 0, and within one fp32 unit on cls_label."""
+    pts, centres, count = torch.as_tensor(pts), torch.as_tensor(centres), torch.as_tensor(count)
+    if pts.is_cuda and pts.dtype == torch.float32 and centres.is_cuda and centres.dtype == torch.float32 and count.is_cuda:
+        from . import compat as _C
+        return _C.rpn_center_labels(pts.contiguous(), centres.contiguous(), count.to(torch.int32).contiguous(), gauss_height, gauss_status,
+                                    gauss_cov)
+    p, c, k = pts.detach().cpu().numpy(), centres.detach().cpu().numpy(), count.detach().cpu().numpy()
+    labels = [gaussian_center_labels(p[b, :, :3], c[b, :max(int(k[b]), 0)], gauss_height, gauss_status, gauss_cov) for b in range(p.shape[0])]
+    cls = np.stack([np.asarray(l[0], dtype=np.float32) for l in labels]) if labels else np.zeros(p.shape[:2], np.float32)
+    reg = np.stack([l[1] for l in labels]) if labels else np.zeros(p.shape[:2] + (3,), np.float32)
+    return torch.from_numpy(cls).to(pts.device), torch.from_numpy(reg).to(pts.device)
+
+
+class _RpnLossFn(torch.autograd.Function):
+    """value and gradient from ``ws3d_rpn_loss``; the backward only scales the saved gradients"""
+
+    @staticmethod
+    def forward(ctx, rpn_cls, rpn_reg, cls_label, reg_label, loc_scope, loc_bin_size, loss_weight):
+        from . import compat as _C
+        vals, counts, g_cls, g_reg = _C.rpn_loss(rpn_cls.contiguous(), rpn_reg.contiguous(), cls_label.contiguous(), reg_label.contiguous(),
+                                                 loc_scope, loc_bin_size, FOCAL_ALPHA, FOCAL_GAMMA, loss_weight)
+        ctx.save_for_backward(g_cls, g_reg)
+        ctx.mark_non_differentiable(vals, counts)
+        return vals[0].clone(), vals, counts
+
+    @staticmethod
+    def backward(ctx, grad_loss, _vals, _counts):
+        g_cls, g_reg = ctx.saved_tensors
+        return grad_loss * g_cls, grad_loss * g_reg, None, None, None, None, None
+
+
+def rpn_loss_fused(rpn_cls: torch.Tensor, rpn_reg: torch.Tensor, cls_label: torch.Tensor, reg_label: torch.Tensor, loc_scope: float,
+                   loc_bin_size: float, loss_weight=LOSS_WEIGHT):
+    """``rpn_loss(..., gaussian_center=True, lazy=True)`` from fused HIP (``ws3d_rpn_loss``, csrc/rpn_targets.hip): rpn_cls (B,N,1),
+    rpn_reg (B,N,4*bins), cls_label (B,N), reg_label (B,N,3) -> (loss, tb).  No boolean-mask indexing, no host branch on the foreground
+    count, nothing read back: tb holds the keys of ``rpn_loss(lazy=True)`` -- ``rpn_fg_sum`` too -- as 0-dim device tensors, for
+    ``resolve_scalars``.  On CPU or non-float32 tensors: ``rpn_loss(lazy=True)`` itself."""
+    tensors = (rpn_cls, rpn_reg, cls_label, reg_label)
+    if not all(t.is_cuda and t.dtype == torch.float32 for t in tensors):
+        return rpn_loss(rpn_cls, rpn_reg, cls_label, reg_label, loc_scope, loc_bin_size, loss_weight=loss_weight, lazy=True)
+    rows = rpn_reg.size(0) * rpn_reg.size(1)
+    loss, vals, counts = _RpnLossFn.apply(rpn_cls.reshape(rows), rpn_reg.reshape(rows, -1), cls_label.detach().reshape(rows),
+                                          reg_label.detach().reshape(rows, 3), loc_scope, loc_bin_size, tuple(loss_weight))
+    tb = {"rpn_loss_cls_pos": vals[3], "rpn_loss_cls_neg": vals[4], "rpn_loss_cls": vals[1], "rpn_loss_reg": vals[2], "rpn_loss": vals[0],
+          "rpn_fg_sum": counts[0]}
     return loss, tb
 
 

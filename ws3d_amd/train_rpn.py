@@ -12,7 +12,9 @@ accepted for command-line compatibility: the weaklyRPN.yaml values live in ``sta
     betas (mom, 0.99), decoupled weight decay p *= 1 - wd*lr on every parameter (fastai
     ``OptimWrapper(true_wd=True, bn_wd=True)``), one-cycle cosine lr / momentum schedule stepped
     every iteration; gradient-norm clipping at 1.0; BN-momentum step decay (train_rpn.py:113-118);
-  * the loss (``ws3d_amd.losses.rpn_loss``) on Gaussian centre labels;
+  * the loss (``ws3d_amd.losses.rpn_loss``) on Gaussian centre labels -- made per scene on the host like the
+    reference's; ``--device_targets`` uploads scenes and centres instead, makes the labels on the device
+    (``losses.center_labels_batch``) and takes loss and gradient from fused HIP (``losses.rpn_loss_fused``);
   * checkpoints ``ckpt/checkpoint_iter_%05d.pth`` = {'it', 'model_state', 'optimizer_state'}
     (train_utils.py:67-99) -- ``model_state`` interchanges with the reference (identical keys).
   * scene augmentation (rotation / scaling / flip, ``losses.scene_augmentation``) and the evaluation
@@ -167,12 +169,14 @@ def load_checkpoint(model: Optional[nn.Module] = None, optimizer=None, filename:
 # ----------------------------------------------------------------------------- data
 class SyntheticCenters:
     """`count` seeded KITTI-shaped scenes with car-centre annotations (the weak labels of WS3D are
-    BEV centre clicks): {'pts_input' (N,4), 'gt_centers' (K,3), 'rpn_cls_label', 'rpn_reg_label'}"""
+    BEV centre clicks): {'pts_input' (N,4), 'gt_centers' (K,3), 'rpn_cls_label', 'rpn_reg_label'}.
+    labels=False: the two label entries are left out and not computed (they are made on the device, ``train(device_targets=True)``);
+    scenes, augmentation and the draws from `rng` are the same either way."""
 
-    def __init__(self, count: int, npoints: int = 16384, config_id: int = 8, augment: bool = False, rng=np.random):
+    def __init__(self, count: int, npoints: int = 16384, config_id: int = 8, augment: bool = False, rng=np.random, labels: bool = True):
         from . import synth
         self.synth, self.count, self.npoints, self.config_id = synth, count, npoints, config_id
-        self.augment, self.rng = augment, rng
+        self.augment, self.rng, self.labels = augment, rng, labels
         self._scenes, self._items = {}, {}   # generated scans (and, without augmentation, their labels) are kept
 
     def __len__(self):
@@ -190,9 +194,10 @@ class SyntheticCenters:
             xyz, centres, _ = losses.scene_augmentation(pc[:, :3], centres, self.rng)
             pc = np.concatenate((xyz.astype(np.float32), pc[:, 3:]), axis=1)
             centres = centres.astype(np.float32)
-        cls, reg = losses.gaussian_center_labels(pc[:, :3], centres)
-        item = {"sample_id": i, "pts_input": pc, "gt_centers": centres, "rpn_cls_label": cls.astype(np.float32),
-                "rpn_reg_label": reg}
+        item = {"sample_id": i, "pts_input": pc, "gt_centers": centres}
+        if self.labels:
+            cls, reg = losses.gaussian_center_labels(pc[:, :3], centres)
+            item.update({"rpn_cls_label": cls.astype(np.float32), "rpn_reg_label": reg})
         if not self.augment:
             self._items[i] = item
         return item
@@ -201,11 +206,12 @@ class SyntheticCenters:
 class KittiCenters:
     """KITTI directory: scans through ``kitti_io`` (no augmentation), centre annotations from
     label_2 (``noise_kind`` selects another label directory like the reference's --noise_kind), the
-    first ``weakly_num`` scenes that contain a Car/Van"""
+    first ``weakly_num`` scenes that contain a Car/Van.  labels=False: items carry 'pts_input' and 'gt_centers' only (see
+    SyntheticCenters)"""
 
     def __init__(self, root: str, split: str = "train", npoints: int = 16384, noise_kind: Optional[str] = None,
-                 weakly_num: int = 500, rng=np.random, augment: bool = False):
-        self.augment = augment
+                 weakly_num: int = 500, rng=np.random, augment: bool = False, labels: bool = True):
+        self.augment, self.labels = augment, labels
         self.scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=rng)
         self.label_sub = noise_kind or "label_2"
         keep = []
@@ -238,9 +244,11 @@ class KittiCenters:
             xyz, centres, _ = losses.scene_augmentation(pts[:, :3], centres, self.scenes.rng)
             pts = np.concatenate((xyz, pts[:, 3:]), axis=1)
             centres = centres.astype(np.float32)
-        cls, reg = losses.gaussian_center_labels(pts[:, :3], centres)
-        return {"sample_id": sid, "pts_input": pts.astype(np.float32), "gt_centers": centres,
-                "rpn_cls_label": cls.astype(np.float32), "rpn_reg_label": reg}
+        item = {"sample_id": sid, "pts_input": pts.astype(np.float32), "gt_centers": centres}
+        if self.labels:
+            cls, reg = losses.gaussian_center_labels(pts[:, :3], centres)
+            item.update({"rpn_cls_label": cls.astype(np.float32), "rpn_reg_label": reg})
+        return item
 
 
 def _collate(items) -> dict:
@@ -250,8 +258,30 @@ def _collate(items) -> dict:
             "sample_id": [s["sample_id"] for s in items]}
 
 
+def _collate_centers(items) -> dict:
+    """the batch of the device-target route: scenes and their annotated centres, no labels.  'gt_centers' (B,Kmax,3) is padded with
+    zeros behind each scene's 'gt_count' (B,) int32 centres (Kmax = the batch's largest count, 0 when no scene has one); label entries
+    an item may carry are dropped"""
+    count = np.array([np.asarray(s["gt_centers"]).reshape(-1, 3).shape[0] for s in items], dtype=np.int32)
+    centres = np.zeros((len(items), int(count.max()) if len(items) else 0, 3), dtype=np.float32)
+    for b, s in enumerate(items):
+        centres[b, :count[b]] = np.asarray(s["gt_centers"], dtype=np.float32).reshape(-1, 3)
+    return {"pts_input": np.stack([s["pts_input"] for s in items]).astype(np.float32), "gt_centers": centres, "gt_count": count,
+            "sample_id": [s["sample_id"] for s in items]}
+
+
+def device_labels(batch: dict, device) -> dict:
+    """a ``_collate_centers`` batch -> {'pts_input', 'rpn_cls_label', 'rpn_reg_label'} tensors on `device`: scenes, centres and counts go
+    up, the labels are made there (``losses.center_labels_batch``: one HIP launch on the current stream; numpy on a CPU device)"""
+    pts = torch.from_numpy(np.ascontiguousarray(batch["pts_input"], dtype=np.float32)).to(device)
+    centres = torch.from_numpy(np.ascontiguousarray(batch["gt_centers"], dtype=np.float32)).to(device)
+    count = torch.from_numpy(np.ascontiguousarray(batch["gt_count"], dtype=np.int32)).to(device)
+    cls, reg = losses.center_labels_batch(pts, centres, count)
+    return {"pts_input": pts, "rpn_cls_label": cls, "rpn_reg_label": reg}
+
+
 def batches(dataset, batch_size: int, rng: np.random.RandomState, rank: int = 0, world: int = 1, workers: int = 0,
-            ahead: int = 3) -> Iterator[dict]:
+            ahead: int = 3, collate=_collate) -> Iterator[dict]:
     """endless shuffled mini-batches (drop_last, like the reference's DataLoader); with world > 1
     every rank takes its own slice of each global batch.  workers > 0 (the reference's --workers):
     the scenes of the next `ahead` batches are read / sampled / labelled by that many forked
@@ -269,7 +299,7 @@ def batches(dataset, batch_size: int, rng: np.random.RandomState, rank: int = 0,
 
     worker_seed = int(rng.get_state()[1][0]) % (2 ** 31)      # derived without drawing: the batch order must not depend on `workers`
     for items in loader.item_batches(dataset, id_batches(), workers, ahead, seed=worker_seed):
-        yield _collate(items)
+        yield collate(items)
 
 
 class DevicePrefetcher:
@@ -286,7 +316,9 @@ class DevicePrefetcher:
     competes with the kernel-launching thread for the interpreter lock).
     ``next()`` yields dicts of DEVICE tensors: ``pts_input``, ``rpn_cls_label`` / ``rpn_reg_label``
     (float32), ``sampling_plan``, plus ``sample_id``; the current stream is made to wait for the
-    upload + sampling first."""
+    upload + sampling first.  A source batch without labels (``_collate_centers``: 'gt_centers' +
+    'gt_count') gets them here: centres and counts are uploaded and ``device_labels`` makes the labels on
+    the side stream, next to the sampling plan -- the same two entries come out."""
 
     KEYS = ("pts_input", "rpn_cls_label", "rpn_reg_label")
 
@@ -307,10 +339,13 @@ class DevicePrefetcher:
             return
         with torch.no_grad(), torch.cuda.stream(self.side):
             out = {"sample_id": batch.get("sample_id")}
-            for key in self.KEYS:
-                # plain pageable upload: staging through pinned buffers + non_blocking copies was measured
-                # slower here (36 vs 23 ms per iteration at batch 8)
-                out[key] = torch.from_numpy(np.ascontiguousarray(batch[key], dtype=np.float32)).to(self.device)
+            if "rpn_cls_label" not in batch:
+                out.update(device_labels(batch, self.device))
+            else:
+                for key in self.KEYS:
+                    # plain pageable upload: staging through pinned buffers + non_blocking copies was measured
+                    # slower here (36 vs 23 ms per iteration at batch 8)
+                    out[key] = torch.from_numpy(np.ascontiguousarray(batch[key], dtype=np.float32)).to(self.device)
             xyz = out["pts_input"][..., 0:3].contiguous()
             if self.timing is not None:
                 t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -350,20 +385,28 @@ def _on_device(x, device) -> torch.Tensor:
 
 # ----------------------------------------------------------------------------- training
 def train_step(model: nn.Module, optimizer: AdamOneCycle, batch: dict, it: int, net_cfg: stage1.RPNConfig,
-               train_cfg: TrainConfig, device, overlap=None) -> dict:
+               train_cfg: TrainConfig, device, overlap=None, fused_loss: bool = False) -> dict:
     """one iteration of Trainer._train_it (train_utils.py:137-147) with the per-iteration schedules.
-    overlap: host work to do once the backward pass is enqueued (DevicePrefetcher.advance)"""
+    overlap: host work to do once the backward pass is enqueued (DevicePrefetcher.advance)
+    fused_loss: ``losses.rpn_loss_fused`` (value and gradient from fused HIP, no read-back in the middle of the step) instead of
+    ``losses.rpn_loss``; a batch that carries centres instead of labels gets its labels on the device first"""
     set_bn_momentum(model, bn_momentum_at(it, train_cfg))
     optimizer.schedule(it)
     if not model.training:
         model.train()
     optimizer.zero_grad()
+    if "rpn_cls_label" not in batch:
+        batch = {**batch, **device_labels(batch, device)}
     inputs = {"pts_input": _on_device(batch["pts_input"], device)}
     if batch.get("sampling_plan") is not None:
         inputs["sampling_plan"] = batch["sampling_plan"]
     out = model(inputs)
-    loss, tb = losses.rpn_loss(out["rpn_cls"], out["rpn_reg"], _on_device(batch["rpn_cls_label"], device),
-                               _on_device(batch["rpn_reg_label"], device), net_cfg.loc_scope, net_cfg.loc_bin_size, lazy=True)
+    if fused_loss:
+        loss, tb = losses.rpn_loss_fused(out["rpn_cls"], out["rpn_reg"], _on_device(batch["rpn_cls_label"], device),
+                                         _on_device(batch["rpn_reg_label"], device), net_cfg.loc_scope, net_cfg.loc_bin_size)
+    else:
+        loss, tb = losses.rpn_loss(out["rpn_cls"], out["rpn_reg"], _on_device(batch["rpn_cls_label"], device),
+                                   _on_device(batch["rpn_reg_label"], device), net_cfg.loc_scope, net_cfg.loc_bin_size, lazy=True)
     loss.backward()
     if overlap is not None:
         overlap()
@@ -387,6 +430,9 @@ def evaluate(model: nn.Module, dataset, net_cfg: stage1.RPNConfig = stage1.DEFAU
     tot_loss, n, pt_hit, pt_fg, gt_hit, gt_cnt, offs = 0.0, 0, 0.0, 0.0, 0, 0, []
     for i in range(len(dataset) if max_scenes is None else min(max_scenes, len(dataset))):
         s = dataset[i]
+        if "rpn_cls_label" not in s:          # a labels=False dataset
+            cls, reg = losses.gaussian_center_labels(s["pts_input"][:, :3], np.asarray(s["gt_centers"], dtype=np.float32).reshape(-1, 3))
+            s = {**s, "rpn_cls_label": cls.astype(np.float32), "rpn_reg_label": reg}
         pts = torch.from_numpy(s["pts_input"][None].astype(np.float32)).to(dev)
         out = model({"pts_input": pts})
         label = torch.from_numpy(s["rpn_cls_label"][None]).to(dev).float()
@@ -415,10 +461,13 @@ def evaluate(model: nn.Module, dataset, net_cfg: stage1.RPNConfig = stage1.DEFAU
 def train(dataset, total_iters: int, batch_size: int, output_dir: Optional[str] = None, ckpt: Optional[str] = None,
           pretrain_ckpt: Optional[str] = None, ckpt_save_interval: int = 20, seed: int = 0, device: str = "cuda:0",
           net_cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, train_cfg: TrainConfig = TrainConfig(), logger=None,
-          distributed: bool = False, prefetch: bool = True, workers: int = 0) -> dict:
+          distributed: bool = False, prefetch: bool = True, workers: int = 0, device_targets: bool = False) -> dict:
     """-> {'model', 'optimizer', 'it', 'history' (loss per iteration), 'checkpoints'}
     prefetch: build / upload the next batch and run its furthest point sampling on a side stream
-    while the current step computes (DevicePrefetcher); same losses either way."""
+    while the current step computes (DevicePrefetcher); same losses either way.
+    device_targets: scenes and centres go up instead of labels (``_collate_centers``; give a ``labels=False`` dataset to skip the host
+    label computation), the labels are made on the device -- by the prefetcher on its side stream, inside the step without one -- and
+    the loss is ``losses.rpn_loss_fused``.  Off by default: the host route of the reference."""
     log = logger or logging.getLogger("ws3d_amd.train_rpn")
     rank, world = 0, 1
     if distributed:
@@ -442,12 +491,13 @@ def train(dataset, total_iters: int, batch_size: int, output_dir: Optional[str] 
     per_epoch = max(len(dataset) // (batch_size * world), 1)
     n_epochs = max(int(total_iters / per_epoch), 1)
     save_every = max(int(n_epochs / min(n_epochs, ckpt_save_interval)), 1) * per_epoch
-    source = batches(dataset, batch_size, np.random.RandomState(seed), rank, world, workers=workers)
+    source = batches(dataset, batch_size, np.random.RandomState(seed), rank, world, workers=workers,
+                     collate=_collate_centers if device_targets else _collate)
     stream = DevicePrefetcher(source, dev, net_cfg.npoints) if prefetch and dev.type == "cuda" else source
     history, saved = [], []
     try:
         return _train_loop(net, model, optimizer, stream, it, total_iters, net_cfg, train_cfg, dev, rank, log, ckpt_dir,
-                           save_every, history, saved)
+                           save_every, history, saved, fused_loss=device_targets)
     finally:
         if isinstance(stream, DevicePrefetcher):
             stream.close()
@@ -455,11 +505,11 @@ def train(dataset, total_iters: int, batch_size: int, output_dir: Optional[str] 
 
 
 def _train_loop(net, model, optimizer, stream, it, total_iters, net_cfg, train_cfg, dev, rank, log, ckpt_dir, save_every,
-                history, saved) -> dict:
+                history, saved, fused_loss: bool = False) -> dict:
     t_mark, it_mark, step_ms = time.perf_counter(), it, []
     while it < total_iters:
         ahead = stream.advance if isinstance(stream, DevicePrefetcher) and it + 1 < total_iters else None
-        tb = train_step(net, optimizer, next(stream), it, net_cfg, train_cfg, dev, overlap=ahead)
+        tb = train_step(net, optimizer, next(stream), it, net_cfg, train_cfg, dev, overlap=ahead, fused_loss=fused_loss)
         it += 1
         history.append(tb["loss"])
         if rank == 0 and (it % 10 == 0 or it == total_iters):
@@ -492,6 +542,8 @@ def main():
     ap.add_argument("--no_prefetch", action="store_true", default=False,
                     help="build / upload / sample the next batch inside the step instead of one step ahead")
     ap.add_argument("--synthetic", type=int, default=0, help="train on this many seeded synthetic scenes instead")
+    ap.add_argument("--device_targets", action="store_true", default=False,
+                    help="upload scenes and centres, make the labels on the device and take the loss from fused HIP (off: labels on the host)")
     a = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s  %(levelname)5s  %(message)s")
     out_dir = a.output_dir or os.path.join("output", "rpn", "weaklyRPN")
@@ -501,14 +553,15 @@ def main():
         from . import dist as wdist
         _, _, local = wdist.init()
     if a.synthetic:
-        ds = SyntheticCenters(a.synthetic)
+        ds = SyntheticCenters(a.synthetic, labels=not a.device_targets)
     elif a.data_root:
         label_dir = a.noise_kind if os.path.isdir(os.path.join(a.data_root, "training", a.noise_kind)) else None
-        ds = KittiCenters(a.data_root, "train", noise_kind=label_dir, weakly_num=a.weakly_num)
+        ds = KittiCenters(a.data_root, "train", noise_kind=label_dir, weakly_num=a.weakly_num, labels=not a.device_targets)
     else:
         ap.error("give --data_root or --synthetic N")
     res = train(ds, a.total_iters, a.batch_size, out_dir, a.ckpt, a.pretrain_ckpt, a.ckpt_save_interval,
-                device=f"cuda:{local}", distributed=distributed, prefetch=not a.no_prefetch, workers=a.workers)
+                device=f"cuda:{local}", distributed=distributed, prefetch=not a.no_prefetch, workers=a.workers,
+                device_targets=a.device_targets)
     if int(os.environ.get("RANK", "0")) == 0:
         logging.getLogger("ws3d_amd.train_rpn").info("done: it %d, last checkpoint %s, median %.1f ms/it", res["it"],
                                                      res["checkpoints"][-1] if res["checkpoints"] else None,
