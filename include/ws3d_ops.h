@@ -829,6 +829,17 @@ WS3D_API int ws3d_rpn_loss(int rows, int bins, double loc_scope, double loc_bin_
                            float *vals, int32_t *counts, float *grad_cls, float *grad_reg, void *workspace, size_t workspace_bytes,
                            ws3d_stream_t stream);
 
+/* ------------------------------------------------- test hooks */
+
+/* What ws3d_roipool3d / _fill / _ws would launch for these sizes under this process's WS3D_ROI_* knobs, without launching it:
+ * 1000 * family + 100 * G + CR -- family 0: roipool3d_kernel<G, CR> (G boxes per workgroup), 1: roipool3d_pipe_kernel<G, CR> (G boxes
+ * per pass), 2: roi_bin_kernel + roipool3d_binned_kernel<CR> (G = 1); CR: rows per LDS stretch of the copy, 0 = the direct copy.
+ * 0: nothing to launch (no scene or no box); the launcher's negative error code where it would refuse the sizes.
+ * aligned16: pts_feature and pooled_features are 16-byte aligned; workspace_bytes: what ws3d_roipool3d_ws is given (0: none).
+ * The launcher decides through the same function.  No HIP call.  (tests/test_roipool_plan.py) */
+WS3D_API int ws3d_roipool3d_plan(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num, int aligned16,
+                                 size_t workspace_bytes);
+
 #ifdef __cplusplus
 }
 #endif

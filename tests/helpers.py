@@ -184,3 +184,43 @@ def greedy_nms_from_iou(iou: np.ndarray, thresh: float) -> np.ndarray:
         keep.append(i)
         removed[i + 1:] |= iou[i, i + 1:] > thresh
     return np.asarray(keep, dtype=np.int64)
+
+
+# ----------------------------------------------------------------------------- roipool3d launch variants
+# The environment knobs of csrc/roipool3d.hip (read once per process) under which tests/test_gpu_parity.py runs every pooling kernel on
+# the GPU and tests/test_roipool_plan.py asks the launcher's plan on the CPU.  compat hands a workspace to every scene of >= 16384
+# points, and a launch with a workspace takes the binned kernel before it looks at WS3D_ROI_PIPE: only the variants with
+# WS3D_ROI_BINNED=0 reach roipool3d_pipe_kernel there.
+def _roi_env(**kw):
+    return {"WS3D_ROI_" + k: str(v) for k, v in kw.items()}
+
+
+ROI_ENV_VARIANTS = [
+    _roi_env(BG=4, PIPE=0, STAGE=0),      # round-1 copy: aligned loads, row-shifted stores
+    _roi_env(BG=4, PIPE=0, STAGE=16), _roi_env(BG=4, PIPE=0, STAGE=32),
+    _roi_env(BG=4, PIPE=2), _roi_env(BG=4, PIPE=2, STAGE=32),
+    _roi_env(BG=4, PIPE=1), _roi_env(BG=4, PIPE=1, STAGE=32),
+    _roi_env(BG=1, STAGE=16), _roi_env(BG=2),
+    # without the binned kernel: the four roipool3d_pipe_kernel instantiations, and roipool3d_kernel<4, 32> / <2, 16> on large scenes
+    _roi_env(BINNED=0, BG=4, PIPE=2), _roi_env(BINNED=0, BG=4, PIPE=2, STAGE=32),
+    _roi_env(BINNED=0, BG=4, PIPE=1), _roi_env(BINNED=0, BG=4, PIPE=1, STAGE=32),
+    _roi_env(BINNED=0, BG=4, PIPE=0, STAGE=32),
+    _roi_env(BG=2, STAGE=16),
+]
+ROI_PIPE_VARIANTS = [v for v in ROI_ENV_VARIANTS if v.get("WS3D_ROI_BINNED") == "0" and v["WS3D_ROI_PIPE"] != "0"]
+
+
+def roi_env_id(env):
+    return ",".join(f"{k[9:]}={v}" for k, v in env.items())
+
+
+# (B, N, M, C, S) and the synth seed of each case.  The last two are the smallest shapes at which the shared phases of the kernels can
+# still go wrong: N at and just past the 16384-point switch (16400 is no multiple of 256), M % 4 == 3 (a last workgroup of three boxes:
+# with two boxes per pass the second pass scans one box and one dummy), C = 4 (one lane per row carries features), S = 8 below one
+# stretch of 16 rows, S = 20 one full stretch and a ragged one of 4 rows.
+ROI_VARIANT_CASES = [(2, 20000, 37, 128, 512), (1, 40000, 9, 128, 64), (2, 3000, 24, 128, 512), (2, 20000, 18, 8, 36), (1, 17000, 6, 5, 33),
+                     (1, 16384, 7, 4, 8), (1, 16400, 11, 4, 20)]
+ROI_VARIANT_SEEDS = [30, 31, 32, 33, 34, 60, 61]
+# (B, n, m, c, s, cfg) of test_roipool3d_bit_exact (default environment)
+ROI_BIT_EXACT_CASES = [(2, 2048, 24, 8, 64, 1), (2, 16384, 100, 128, 512, 3), (1, 4096, 40, 16, 512, 2), (1, 512, 8, 3, 16, 4),
+                       (1, 65536, 64, 128, 512, 5), (1, 1000, 5, 1, 700, 6)]

@@ -8,6 +8,7 @@ import pytest
 
 torch = pytest.importorskip("torch")
 
+from tests import helpers as H  # noqa: E402
 from ws3d_amd import synth  # noqa: E402
 
 pytestmark = pytest.mark.gpu
@@ -594,8 +595,7 @@ def _roi_scene(B, n, m, c, cfg):
     return pc[:, :, :3].copy(), boxes, feat
 
 
-@pytest.mark.parametrize("B,n,m,c,s,cfg", [(2, 2048, 24, 8, 64, 1), (2, 16384, 100, 128, 512, 3), (1, 4096, 40, 16, 512, 2),
-                                           (1, 512, 8, 3, 16, 4), (1, 65536, 64, 128, 512, 5), (1, 1000, 5, 1, 700, 6)])
+@pytest.mark.parametrize("B,n,m,c,s,cfg", H.ROI_BIT_EXACT_CASES)
 def test_roipool3d_bit_exact(ops, oracle, B, n, m, c, s, cfg):
     xyz, boxes, feat = _roi_scene(B, n, m, c, cfg)
     from ws3d_amd import kitti_utils
@@ -702,38 +702,42 @@ def test_roipool3d_boxes_wider_than_the_ten_metre_window(ops, oracle):
         np.testing.assert_array_equal(host(pooled), ref_p)
 
 
-ROI_ENV_VARIANTS = [
-    {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "0", "WS3D_ROI_STAGE": "0"},     # round-1 copy: aligned loads, row-shifted stores
-    {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "0", "WS3D_ROI_STAGE": "16"}, {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "0", "WS3D_ROI_STAGE": "32"},
-    {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "2"}, {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "2", "WS3D_ROI_STAGE": "32"},
-    {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "1"}, {"WS3D_ROI_BG": "4", "WS3D_ROI_PIPE": "1", "WS3D_ROI_STAGE": "32"},
-    {"WS3D_ROI_BG": "1", "WS3D_ROI_STAGE": "16"}, {"WS3D_ROI_BG": "2"},
-]
-
-
-@pytest.mark.parametrize("env", ROI_ENV_VARIANTS, ids=lambda e: ",".join(f"{k[9:]}={v}" for k, v in e.items()))
-def test_roipool3d_kernel_variants_subprocess(oracle, tmp_path, env):
-    """every selectable roipool3d kernel (boxes per workgroup, direct / LDS-staged copy, the variant that overlaps scan and
-    copy): pooled rows, empty flags and selected indices against the oracle; scenes above and below the 16384-point switch,
-    a box count that leaves a ragged last workgroup, empty boxes, pre-zeroed and fill entry points"""
-    import subprocess, sys, os, textwrap
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cases = [(2, 20000, 37, 128, 512), (1, 40000, 9, 128, 64), (2, 3000, 24, 128, 512), (2, 20000, 18, 8, 36), (1, 17000, 6, 5, 33)]
+@pytest.fixture(scope="module")
+def roi_variant_refs(oracle, tmp_path_factory):
+    """the scenes of H.ROI_VARIANT_CASES as in<i>.npz in one directory, and the oracle's (pooled, empty, idx) of each: built once,
+    shared by every variant"""
+    d = tmp_path_factory.mktemp("roi_variants")
     refs = []
-    for i, (B, N, M, C, S) in enumerate(cases):
-        pc = synth.make_batch("lidar", B, N, 30 + i)[:, :, :3].copy()
-        boxes = synth.proposal_boxes(B, M, 30 + i)
+    for i, ((B, N, M, C, S), seed) in enumerate(zip(H.ROI_VARIANT_CASES, H.ROI_VARIANT_SEEDS)):
+        pc = synth.make_batch("lidar", B, N, seed)[:, :, :3].copy()
+        boxes = synth.proposal_boxes(B, M, seed)
         boxes[0, 1:3, 0] += 400.0                                             # empty boxes
         boxes[-1, 3::5, 4:6] = (25.0, 30.0)                                   # wider than the +-10 m window of pt_in_box3d
+        if i >= 5:                                                            # a tiny box on a point of the cloud: a wrap-padded list
+            boxes[0, 4] = (*pc[0, N // 3], 0.5, 0.5, 0.5, 0.3)
+            boxes[0, 4, 1] += 0.25
         feat = np.random.default_rng(i).standard_normal((B, N, C)).astype(np.float32)
-        np.savez(tmp_path / f"in{i}.npz", pc=pc, boxes=boxes, feat=feat)
+        np.savez(d / f"in{i}.npz", pc=pc, boxes=boxes, feat=feat)
         refs.append(oracle.roipool3d(pc, boxes, feat, S, return_idx=True))
+    return d, refs
+
+
+@pytest.mark.parametrize("env", H.ROI_ENV_VARIANTS, ids=H.roi_env_id)
+def test_roipool3d_kernel_variants_subprocess(roi_variant_refs, tmp_path, env):
+    """every selectable roipool3d kernel (boxes per workgroup, direct / LDS-staged copy, the variant that overlaps scan and
+    copy -- reached only with WS3D_ROI_BINNED=0, tests/test_roipool_plan.py checks which kernel each variant takes): pooled rows,
+    empty flags and selected indices against the oracle; scenes above and below the 16384-point switch, box counts that leave a
+    ragged last workgroup, empty, wrap-padded and truncated boxes in every scene, pre-zeroed and fill entry points"""
+    import subprocess, sys, os, textwrap
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cases = H.ROI_VARIANT_CASES
+    src, refs = roi_variant_refs
     code = textwrap.dedent(f"""
         import sys, numpy as np, torch
         sys.path.insert(0, {root!r})
         from ws3d_amd import compat
         for i, S in enumerate({[c[4] for c in cases]!r}):
-            d = np.load({str(tmp_path)!r} + f"/in{{i}}.npz")
+            d = np.load({str(src)!r} + f"/in{{i}}.npz")
             pc, boxes, feat = (torch.from_numpy(d[k]).cuda() for k in ("pc", "boxes", "feat"))
             B, M, C = boxes.shape[0], boxes.shape[1], feat.shape[2]
             out = {{}}
@@ -749,7 +753,11 @@ def test_roipool3d_kernel_variants_subprocess(oracle, tmp_path, env):
     assert r.returncode == 0, r.stderr[-2000:]
     for i, (rp, re, rs) in enumerate(refs):
         got = np.load(tmp_path / f"out{i}.npz")
+        S = cases[i][4]
+        distinct = np.array([len(np.unique(row)) for row in rs.reshape(-1, S)])[re.reshape(-1) == 0]
         assert (re == 1).sum() >= 2
+        if i >= 5:      # the two small cases: a wrap-padded list and a truncated one beside the empty boxes
+            assert ((distinct >= 1) & (distinct < S)).sum() >= 1 and (distinct == S).sum() >= 1, (cases[i], distinct)
         for k in "zf":
             np.testing.assert_array_equal(got[k + "e"], re, err_msg=str((cases[i], k)))
             np.testing.assert_array_equal(got[k + "p"], rp, err_msg=str((cases[i], k)))

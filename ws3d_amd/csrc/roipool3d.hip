@@ -103,10 +103,159 @@ __device__ __forceinline__ void roi_scene_group(int batch, int groups, int &b, i
     }
 }
 
+// ---- the phases the three pooling kernels are built from (256 lanes per workgroup) -----------------------
+
+// Scan, loads: the 4 x 64 points of one trip of a wave, k0 = the lane's point of the first sub-block.  Loads are clamped, never
+// branched; a lane past the wave's range [.., end) gets x = NaN = "outside".  ONE 12-byte load per point: three dword loads per
+// point made the scan address-bound (12 wave loads per trip, each spanning six cache lines).
+__device__ __forceinline__ void roi_load_trip(const float *xyz, int k0, int end, int pts_num, float (&x)[4], float (&y)[4], float (&z)[4]) {
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#ifdef WS3D_ROI_NO_SCAN   // ablation: see roi_scan_trip
+        x[u] = __builtin_nanf(""); y[u] = z[u] = 0.f;
+#else
+        const int k = k0 + u * 64;
+        const f3v p = *reinterpret_cast<const f3u *>(xyz + (size_t)min(k, pts_num - 1) * 3);
+        x[u] = k < end ? p.x : __builtin_nanf(""); y[u] = p.y; z[u] = p.z;
+#endif
+    }
+}
+
+// Scan, tests: the points of one trip against the G frames of the wave.  All 4 x G tests first (independent VALU work, masks in
+// SGPRs), bookkeeping afterwards: a test followed directly by its own ballot branch serialises on VALU->SALU round trips.  Hits are
+// appended in point order to the wave's G lists wl[g * 4 * S ..] (the element is v0 + 64 u for sub-block u: an absolute index or an
+// offset into the wave's range); wcnt[g] is wave-uniform, and a full list (wcnt[g] >= S) takes no more appends.  Returns "every
+// list is full".  `first`: the wave's first trip (the ablations key on it).
+template <int G, typename LIST_T>
+__device__ __forceinline__ bool roi_scan_trip(const BoxFrame (&f)[G], bool all_small, const float (&x)[4], const float (&y)[4], const float (&z)[4],
+                                              int v0, bool first, LIST_T *wl, int S, int (&wcnt)[G]) {
+    const int lane = threadIdx.x & 63;
+#ifdef WS3D_ROI_NO_SCAN   // ablation (scripts/ablate_roi.sh): no loads, no tests; every wave pretends it found 40 points
+#pragma unroll
+    for (int g = 0; g < G; ++g)
+        if (wcnt[g] < S) { if (lane < min(40, S)) wl[g * 4 * S + lane] = (LIST_T)(v0 + lane * 6); wcnt[g] = min(40, S); }
+    return true;
+#else
+    uint64_t mask[4][G];
+    if (all_small) {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<true>(f[g], x[u], y[u], z[u]));
+    } else {
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int g = 0; g < G; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<false>(f[g], x[u], y[u], z[u]));
+    }
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+#pragma unroll
+        for (int g = 0; g < G; ++g) {
+#if defined(WS3D_ROI_SCAN_ABL) && WS3D_ROI_SCAN_ABL == 1      // ablation (scripts/ablate_roi_scan.sh): tests without the list appends (one hit keeps them alive)
+            const uint64_t mk = mask[u][g] & (first ? 1ull : 0ull);
+#elif defined(WS3D_ROI_SCAN_ABL) && WS3D_ROI_SCAN_ABL == 2    // ablation: loads and loop only
+            const uint64_t mk = (first && x[u] == 12345.f) ? 1ull : 0ull;
+#else
+            const uint64_t mk = mask[u][g];
+#endif
+            if (mk) {  // wave-uniform
+                const int wc = __builtin_amdgcn_readfirstlane(wcnt[g]);
+                const int pos = wc + mbcnt(mk);
+                if (((mk >> lane) & 1ull) && pos < S) wl[g * 4 * S + pos] = (LIST_T)(v0 + u * 64);
+                wcnt[g] = min(wc + (int)__builtin_popcountll(mk), S);
+            }
+        }
+    }
+    bool all_full = true;
+#pragma unroll
+    for (int g = 0; g < G; ++g) all_full = all_full && wcnt[g] >= S;
+    return all_full;
+#endif
+}
+
+// Selection: the 4 wave lists of a box lg[w * S ..] with wc[w] entries (wave w's elements count from w * base) are concatenated
+// -- their ranges are ordered --, truncated to S and wrap-padded (duplicate_idx = k % cnt, roipool3d_kernel.cu:139-157) into sel[0, S)
+// and, when asked for, idx_out.  Returns cnt = min(entries, S); a box without points (0) writes nothing.
+template <typename LIST_T>
+__device__ __forceinline__ int roi_select(const LIST_T *lg, const int *wc, int S, int base, int *sel, int32_t *idx_out) {
+    const int c0 = wc[0], c1 = wc[1], c2 = wc[2], c3 = wc[3];
+    const int cnt = min(c0 + c1 + c2 + c3, S);
+    if (cnt == 0) return 0;
+    for (int q = threadIdx.x; q < S; q += 256) {
+        int t = q < cnt ? q : q % cnt;
+        int v;
+        if (t < c0) v = lg[t];
+        else if ((t -= c0) < c1) v = base + lg[S + t];
+        else if ((t -= c1) < c2) v = 2 * base + lg[2 * S + t];
+        else v = 3 * base + lg[3 * S + (t - c2)];
+        sel[q] = v;
+        if (idx_out) idx_out[q] = v;
+    }
+    return cnt;
+}
+
+// The empty box (roipool3d_kernel.cu:147-149,181-183): flag it and leave its rows untouched -- or, under `fill`
+// (ws3d_roipool3d_fill: the caller did not pre-zero), write the zeros of an empty box here.
+__device__ __forceinline__ void roi_empty_box(size_t bm, int S, int row, int fill, int32_t *empty_flag, int32_t *pts_idx, float *pooled) {
+    const int tid = threadIdx.x, total = S * row;
+    if (tid == 0) empty_flag[bm] = 1;
+    if (pts_idx)
+        for (int q = tid; q < S; q += 256) pts_idx[bm * S + q] = 0;
+    if (fill) {
+        float *o = pooled + bm * (size_t)total;
+        const float4v zero = {0.f, 0.f, 0.f, 0.f};
+        for (int q = tid * 4; q + 3 < total; q += 1024) *reinterpret_cast<float4u *>(o + q) = zero;
+        for (int q = (total & ~3) + tid; q < total; q += 256) o[q] = 0.f;      // (the direct copy takes blocks of any length)
+    }
+}
+
+// The staged copy of one stretch of CR pooled rows.  Through LDS: a pooled row is 3 + C floats = 524 bytes at C = 128, so a feature
+// row lands 12 bytes off a 16-byte boundary, and 16-byte stores that straddle 16-byte slots run at HALF the write bandwidth of
+// aligned ones on this chip (scripts/ubench/row_copy.hip: 2.5 vs 5.1 TB/s, stores only).  The S x (3+C) block of a box is one
+// contiguous, 16-byte-aligned stream: gather() fetches the rows sel[c0 ..] with aligned 16-byte loads (32 lanes per row, CR / 8
+// rows per lane), deposit_store() puts them into a tight copy in LDS and, after the ONE barrier of the stretch, stores the
+// CR * (3+C) / 4 units of that stretch aligned and non-temporal (the output is never re-read here, the gathered rows are: overlapping
+// boxes share points).  The caller alternates two staging buffers; the pipe kernel runs a scan trip between the two halves.
+// (host: C % 4 == 0, C <= 128, S * (3+C) % 4 == 0, 16-byte-aligned pointers)
+template <int CR>
+struct RoiStretch {
+    static constexpr int RPH = CR / 8;
+    float4v v[RPH];
+    float p3[RPH];
+    __device__ __forceinline__ void gather(const int *sel, int c0, int S, const float *xyz, const float *pts_feature, int feat_len) {
+        const int half = threadIdx.x >> 5, l32 = threadIdx.x & 31, f4 = feat_len >> 2;
+#pragma unroll
+        for (int u = 0; u < RPH; ++u) {
+            const int src = sel[min(c0 + half * RPH + u, S - 1)];
+            v[u] = float4v{0.f, 0.f, 0.f, 0.f};      // defined in every lane: registers left undefined in the lanes that do not load made the
+            p3[u] = 0.f;                             // compiler wait for each load before it issued the next one (+4 % on the binned kernel)
+            if (l32 < f4) v[u] = reinterpret_cast<const float4v *>(pts_feature + (size_t)src * feat_len)[l32];
+            if (l32 < 3) p3[u] = xyz[(size_t)src * 3 + l32];
+        }
+    }
+    __device__ __forceinline__ void deposit_store(float *st, float *out_block, int c0, int S, int row) const {
+        const int tid = threadIdx.x, half = tid >> 5, l32 = tid & 31, f4 = (row - 3) >> 2;
+        const int nr = min(CR, S - c0);
+#pragma unroll
+        for (int u = 0; u < RPH; ++u) {
+            const int r = half * RPH + u;
+            if (r < nr) {
+                if (l32 < f4) *reinterpret_cast<float4u *>(st + r * row + 3 + 4 * l32) = v[u];
+                if (l32 < 3) st[r * row + l32] = p3[u];
+            }
+        }
+        __syncthreads();
+        float4v *o4 = reinterpret_cast<float4v *>(out_block + (size_t)c0 * row);
+        const int units = (nr * row) >> 2;
+        for (int q = tid; q < units; q += 256) __builtin_nontemporal_store(*reinterpret_cast<const float4v *>(st + 4 * q), o4 + q);
+    }
+};
+
 // BG boxes of one scene per workgroup: every point loaded by the scan is tested against BG box
 // frames, so the scene is streamed from L2 once per BG boxes instead of once per box (at config 5
 // the per-box rescans were 3x the output bytes).
-// CR > 0: the copy phase stages CR rows at a time through LDS (see there).
+// CR > 0: the copy phase stages CR rows at a time through LDS (RoiStretch).
 template <int BG, int CR>
 __global__ __launch_bounds__(256) void roipool3d_kernel(int pts_num, int boxes_num, int feat_len,
                                                         int S, const float *__restrict__ xyz,
@@ -144,59 +293,18 @@ __global__ __launch_bounds__(256) void roipool3d_kernel(int pts_num, int boxes_n
     // 4 sub-blocks of 64 points per trip, software-pipelined: the 12 loads of trip t+1 are issued
     // before the tests of trip t, so the L2 round trip hides behind ~500 instructions of tests
     float nx[4], ny[4], nz[4];
-    auto load_trip = [&](int k0) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + u * 64 + lane;   // loads are clamped, never branched; a lane past the
-            // wave's range gets x = NaN = "outside".  ONE 12-byte load per point: three dword loads per point made the scan
-            // address-bound (12 wave loads per trip, each spanning six cache lines)
-            const f3v p = *reinterpret_cast<const f3u *>(xyz + (size_t)min(k, pts_num - 1) * 3);
-            nx[u] = k < end ? p.x : __builtin_nanf(""); ny[u] = p.y; nz[u] = p.z;
-        }
-    };
-#if defined(WS3D_ROI_NO_SCAN)   // ablation: pretend every wave found 40 points
-    for (int g = 0; g < BG; ++g) { if (lane < 40) lists[(g * 4 + w) * S + lane] = start + lane * 7; wcnt[g] = g < nb ? 40 : S; }
-    for (int k0 = end; k0 < end; k0 += 256) {
-#else
-    if (start < end) load_trip(start);
+    // (Register allocation, found by compiling both ways: through a lambda the allocator keeps the x / z register pairs of the packed
+    // tests, called directly every trip grows by 90 moves; but the instantiations with the direct copy end at 171 registers and
+    // two waves per SIMD through the lambda, and at the 97 they always had with the direct call.)
+    auto load_trip = [&](int k0) { roi_load_trip(xyz, k0 + lane, end, pts_num, nx, ny, nz); };
+    if (start < end) roi_load_trip(xyz, start + lane, end, pts_num, nx, ny, nz);
     for (int k0 = start; k0 < end; k0 += 256) {
-#endif
         float x[4], y[4], z[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) { x[u] = nx[u]; y[u] = ny[u]; z[u] = nz[u]; }
-        load_trip(k0 + 256);
-        // all 4 x BG tests first (independent VALU work, masks in SGPRs), bookkeeping afterwards:
-        // a test followed directly by its own ballot branch serialises on VALU->SALU round trips
-        uint64_t mask[4][BG];
-        if (all_small) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int g = 0; g < BG; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<true>(f[g], x[u], y[u], z[u]));
-        } else {
-#pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int g = 0; g < BG; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<false>(f[g], x[u], y[u], z[u]));
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int k = k0 + u * 64 + lane;
-#pragma unroll
-            for (int g = 0; g < BG; ++g) {
-                const uint64_t mk = mask[u][g];
-                if (mk) {  // wave-uniform; a full list (wcnt >= S) takes no more appends: pos < S fails
-                    const int wc = __builtin_amdgcn_readfirstlane(wcnt[g]);
-                    const int pos = wc + mbcnt(mk);
-                    if (((mk >> lane) & 1ull) && pos < S) lists[(g * 4 + w) * S + pos] = k;
-                    wcnt[g] = min(wc + (int)__builtin_popcountll(mk), S);
-                }
-            }
-        }
-        bool all_full = true;
-#pragma unroll
-        for (int g = 0; g < BG; ++g) all_full = all_full && wcnt[g] >= S;
-        if (all_full) break;
+        if constexpr (CR > 0) load_trip(k0 + 256);
+        else roi_load_trip(xyz, k0 + 256 + lane, end, pts_num, nx, ny, nz);
+        if (roi_scan_trip<BG, int>(f, all_small, x, y, z, k0 + lane, k0 == start, lists + w * S, S, wcnt)) break;
     }
     if (lane == 0) {
 #pragma unroll
@@ -210,32 +318,11 @@ __global__ __launch_bounds__(256) void roipool3d_kernel(int pts_num, int boxes_n
     const bool vec_rows = feat_len >= 4 && (feat_len & 3) == 0 && (reinterpret_cast<uintptr_t>(pts_feature) & 15) == 0;
     for (int g = 0; g < nb; ++g) {
         const size_t bm = (size_t)b * boxes_num + box0 + g;
-        const int *lg = lists + g * 4 * S;
-        const int c0 = wcnt_s[g * 4 + 0], c1 = wcnt_s[g * 4 + 1], c2 = wcnt_s[g * 4 + 2], c3 = wcnt_s[g * 4 + 3];
-        const int cnt = min(c0 + c1 + c2 + c3, S);
-        if (cnt == 0) {  // roipool3d_kernel.cu:147-149,181-183: flag the box, leave its rows untouched
-            if (tid == 0) empty_flag[bm] = 1;
-            if (pts_idx)
-                for (int q = tid; q < S; q += 256) pts_idx[bm * S + q] = 0;
-            if (fill) {  // ws3d_roipool3d_fill: the caller did not pre-zero, write the zeros of an empty box here
-                float *o = pooled + bm * (size_t)total;
-                const float4v zero = {0.f, 0.f, 0.f, 0.f};
-                for (int q = tid * 4; q + 3 < total; q += 1024) *reinterpret_cast<float4u *>(o + q) = zero;
-                for (int q = (total & ~3) + tid; q < total; q += 256) o[q] = 0.f;
-            }
+        if (roi_select(lists + g * 4 * S, wcnt_s + g * 4, S, 0, sel, pts_idx ? pts_idx + bm * S : nullptr) == 0) {
+            roi_empty_box(bm, S, row, fill, empty_flag, pts_idx, pooled);
             continue;  // wave-uniform for the whole workgroup
         }
         if (fill && tid == 0) empty_flag[bm] = 0;
-        for (int q = tid; q < S; q += 256) {
-            int t = q < cnt ? q : q % cnt;  // duplicate_idx = k % cnt (roipool3d_kernel.cu:153-157)
-            int v;
-            if (t < c0) v = lg[t];
-            else if ((t -= c0) < c1) v = lg[S + t];
-            else if ((t -= c1) < c2) v = lg[2 * S + t];
-            else v = lg[3 * S + (t - c2)];
-            sel[q] = v;
-            if (pts_idx) pts_idx[bm * S + q] = v;
-        }
         __syncthreads();
 #ifdef WS3D_ROI_NO_COPY
         if (pts_num >= 0) continue;
@@ -245,41 +332,12 @@ __global__ __launch_bounds__(256) void roipool3d_kernel(int pts_num, int boxes_n
             const int src = sel[sr];
             return j < 3 ? xyz[(size_t)src * 3 + j] : pts_feature[(size_t)src * feat_len + (j - 3)];
         };
-        if (CR > 0) {
-            // Through LDS: a pooled row is 3 + C floats = 524 bytes at C = 128, so a feature row lands 12 bytes off a
-            // 16-byte boundary, and 16-byte stores that straddle 16-byte slots run at HALF the write bandwidth of aligned
-            // ones on this chip (scripts/ubench/row_copy.hip: 2.5 vs 5.1 TB/s, stores only).  The S x (3+C) block of a box is
-            // one contiguous, 16-byte-aligned stream: CR rows are gathered with aligned 16-byte loads (32 lanes per row)
-            // into a tight copy in LDS, and the CR * (3+C) / 4 units of that stretch are stored aligned; two buffers, one
-            // barrier per stretch.  (host: C % 4 == 0, C <= 128, S * (3+C) % 4 == 0, 16-byte-aligned pointers)
+        if constexpr (CR > 0) {
             float *stage = reinterpret_cast<float *>(smem) + (((BG * 4 + 1) * S + 3) & ~3);
-            const int half = tid >> 5, l32 = tid & 31;
-            const int f4 = feat_len >> 2;
-            constexpr int RPH = CR > 0 ? CR / 8 : 1;
             for (int c0 = 0, it = 0; c0 < S; c0 += CR, ++it) {
-                float *st = stage + (it & 1) * CR * row;
-                const int nr = min(CR, S - c0);
-                float4v v[RPH];
-                float p3[RPH];
-#pragma unroll
-                for (int u = 0; u < RPH; ++u) {
-                    const int src = sel[min(c0 + half * RPH + u, S - 1)];
-                    if (l32 < f4) v[u] = reinterpret_cast<const float4v *>(pts_feature + (size_t)src * feat_len)[l32];
-                    if (l32 < 3) p3[u] = xyz[(size_t)src * 3 + l32];
-                }
-#pragma unroll
-                for (int u = 0; u < RPH; ++u) {
-                    const int r = half * RPH + u;
-                    if (r < nr) {
-                        if (l32 < f4) *reinterpret_cast<float4u *>(st + r * row + 3 + 4 * l32) = v[u];
-                        if (l32 < 3) st[r * row + l32] = p3[u];
-                    }
-                }
-                __syncthreads();
-                float4v *o4 = reinterpret_cast<float4v *>(out + (size_t)c0 * row);
-                const int units = (nr * row) >> 2;
-                for (int q = tid; q < units; q += 256)
-                    __builtin_nontemporal_store(*reinterpret_cast<const float4v *>(st + 4 * q), o4 + q);
+                RoiStretch<CR> stretch;
+                stretch.gather(sel, c0, S, xyz, pts_feature, feat_len);
+                stretch.deposit_store(stage + (it & 1) * CR * row, out, c0, S, row);
             }
         } else if (vec_rows) {
             // feature rows are 16-byte aligned in the source: 32 lanes move one row with aligned
@@ -343,8 +401,8 @@ __global__ __launch_bounds__(256) void roipool3d_kernel(int pts_num, int boxes_n
 // In roipool3d_kernel every workgroup of the launch scans (VALU-bound), then copies (HBM-bound), all of them in lock-step, so
 // the two phases add (c5: 0.28 + 0.22 ms).  Here the 4 boxes of a workgroup are handled in 4 / SG passes of SG boxes, and the
 // scan loop of pass p carries the copy of pass p-1: each trip of the scan (256 points per wave, ~170 * SG VALU instructions)
-// issues the gathers of one stretch of CR pooled rows before its tests and stores that stretch (through LDS, aligned: see the
-// copy phase of roipool3d_kernel) after them.  The lists hold 16-bit offsets into the wave's quarter of the scene, so a pass needs
+// issues the gathers of one stretch of CR pooled rows before its tests and stores that stretch (through LDS, aligned:
+// RoiStretch) after them.  The lists hold 16-bit offsets into the wave's quarter of the scene, so a pass needs
 // SG * 4 * S * 2 bytes of lists + SG * S * 4 of selected indices + 2 * CR * (3 + C) * 4 of staging.
 // Measured at c5 (scripts/ablate_roi.sh): 0.56 ms (direct copy) -> 0.52 (staged copy) -> 0.47 (this kernel, SG = 2, CR = 16);
 // scan alone 0.26, copy alone 0.25.  What was tried on top and did not help: one box per pass (0.53: the per-pass overhead
@@ -356,9 +414,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
                                                              const float *__restrict__ boxes3d, const float *__restrict__ pts_feature,
                                                              float *__restrict__ pooled, int32_t *__restrict__ empty_flag,
                                                              int32_t *__restrict__ pts_idx, int fill, int batch) {
-    constexpr int BG = 4, RPH = CR / 8;
+    constexpr int BG = 4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int row = 3 + feat_len;
+    __builtin_assume(((S * row) & 3) == 0);            // (roi_plan; roi_empty_box then has no tail)
     float *stage = reinterpret_cast<float *>(smem);                                     // 2 * CR * row
     int *sel = reinterpret_cast<int *>(stage + 2 * CR * row);                           // SG * S: the subgroup being copied
     uint16_t *lists = reinterpret_cast<uint16_t *>(sel + SG * S);                       // SG * 4 * S: the subgroup being scanned
@@ -370,7 +429,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int box0 = grp * BG;
     const int nb = min(BG, boxes_num - box0);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    const int half = tid >> 5, l32 = tid & 31, f4 = feat_len >> 2;
     xyz += (size_t)b * pts_num * 3;
     pts_feature += (size_t)b * pts_num * feat_len;
     const int Q = (((pts_num + 3) / 4 + 63) / 64) * 64;
@@ -378,38 +436,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
     const int trips = (Q + 255) / 256;
     const int cpb = (S + CR - 1) / CR;                                                  // stretches per box
 
-    // ---- the copy of one stretch of CR pooled rows, in two halves around the tests of a scan trip: gathers (aligned 16-byte
-    // loads, 32 lanes per row), then -- through LDS, two buffers, one barrier -- CR * (3+C) / 4 aligned 16-byte stores
-    float4v cv[RPH];
-    float cp3[RPH];
+    // ---- the copy of stretch c of the subgroup at sub0 - SG, in two halves around the tests of a scan trip (RoiStretch)
+    RoiStretch<CR> stretch;
     auto issue = [&](int c) {
-        const int g = c / cpb, c0 = (c - g * cpb) * CR;
+        const int g = c / cpb;
         if (cnt_s[g] == 0) return;
-#pragma unroll
-        for (int u = 0; u < RPH; ++u) {
-            const int src = sel[g * S + min(c0 + half * RPH + u, S - 1)];
-            if (l32 < f4) cv[u] = reinterpret_cast<const float4v *>(pts_feature + (size_t)src * feat_len)[l32];
-            if (l32 < 3) cp3[u] = xyz[(size_t)src * 3 + l32];
-        }
+        stretch.gather(sel + g * S, (c - g * cpb) * CR, S, xyz, pts_feature, feat_len);
     };
     auto finish = [&](int c, int sub0, int parity) {
-        const int g = c / cpb, c0 = (c - g * cpb) * CR;
+        const int g = c / cpb;
         if (cnt_s[g] == 0) return;                                                      // workgroup-uniform
-        float *st = stage + parity * CR * row;
-        const int nr = min(CR, S - c0);
-#pragma unroll
-        for (int u = 0; u < RPH; ++u) {
-            const int r = half * RPH + u;
-            if (r < nr) {
-                if (l32 < f4) *reinterpret_cast<float4u *>(st + r * row + 3 + 4 * l32) = cv[u];
-                if (l32 < 3) st[r * row + l32] = cp3[u];
-            }
-        }
-        __syncthreads();
         const size_t bm = (size_t)b * boxes_num + box0 + sub0 + g;
-        float4v *o4 = reinterpret_cast<float4v *>(pooled + (bm * S + c0) * (size_t)row);
-        const int units = (nr * row) >> 2;
-        for (int q = tid; q < units; q += 256) __builtin_nontemporal_store(*reinterpret_cast<const float4v *>(st + 4 * q), o4 + q);
+        stretch.deposit_store(stage + parity * CR * row, pooled + bm * S * (size_t)row, (c - g * cpb) * CR, S, row);
     };
 
     int parity = 0;
@@ -432,19 +470,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
         for (int g = 0; g < SG; ++g) all_small = all_small && frame_is_small(f[g]);
         float nx[4], ny[4], nz[4];
-        auto load_trip = [&](int k0) {
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int k = k0 + u * 64 + lane;
-                const f3v pp = *reinterpret_cast<const f3u *>(xyz + (size_t)min(k, pts_num - 1) * 3);      // one 12-byte load per point
-                nx[u] = k < end ? pp.x : __builtin_nanf(""); ny[u] = pp.y; nz[u] = pp.z;
-            }
-        };
+        // (a lambda: see roipool3d_kernel; called directly the trip grew by 55 moves and the kernel by 3 %)
+        auto load_trip = [&](int k0) { roi_load_trip(xyz, k0 + lane, end, pts_num, nx, ny, nz); };
         bool done = !scanning || start >= end;
-#ifdef WS3D_ROI_NO_SCAN   // ablation: pretend every wave found 40 points
-        for (int g = 0; g < SG; ++g) { if (lane < 40) lists[(g * 4 + w) * S + lane] = (uint16_t)(lane * 7); if (sub0 + g < nb) wcnt[g] = 40; }
-        done = true;
-#endif
         if (!done) load_trip(start);
         int next_chunk = 0, acc = 0, upto = 0;
         const int ntrips = scanning ? trips : 0;
@@ -459,42 +487,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
 #pragma unroll
                 for (int u = 0; u < 4; ++u) { x[u] = nx[u]; y[u] = ny[u]; z[u] = nz[u]; }
                 load_trip(k0 + 256);
-                uint64_t mask[4][SG];
-                if (all_small) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int g = 0; g < SG; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<true>(f[g], x[u], y[u], z[u]));
-                } else {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u)
-#pragma unroll
-                        for (int g = 0; g < SG; ++g) mask[u][g] = __builtin_amdgcn_ballot_w64(pt_in_frame<false>(f[g], x[u], y[u], z[u]));
-                }
-                bool all_full = true;
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int k = t * 256 + u * 64 + lane;                              // offset into the wave's quarter
-#pragma unroll
-                    for (int g = 0; g < SG; ++g) {
-#if defined(WS3D_ROI_SCAN_ABL) && WS3D_ROI_SCAN_ABL == 1      // ablation: tests without the list appends (one hit keeps them alive)
-                        const uint64_t mk = mask[u][g] & (k0 == start ? 1ull : 0ull);
-#elif defined(WS3D_ROI_SCAN_ABL) && WS3D_ROI_SCAN_ABL == 2    // ablation: loads and loop only
-                        const uint64_t mk = (k0 == start && x[u] == 12345.f) ? 1ull : 0ull;
-#else
-                        const uint64_t mk = mask[u][g];
-#endif
-                        if (mk) {
-                            const int wc = __builtin_amdgcn_readfirstlane(wcnt[g]);
-                            const int pos = wc + mbcnt(mk);
-                            if (((mk >> lane) & 1ull) && pos < S) lists[(g * 4 + w) * S + pos] = (uint16_t)k;
-                            wcnt[g] = min(wc + (int)__builtin_popcountll(mk), S);
-                        }
-                    }
-                }
-#pragma unroll
-                for (int g = 0; g < SG; ++g) all_full = all_full && wcnt[g] >= S;
-                done = all_full;
+                done = roi_scan_trip<SG, uint16_t>(f, all_small, x, y, z, t * 256 + lane, t == 0, lists + w * S, S, wcnt);   // offsets into the wave's quarter
             }
             if (has) { finish(next_chunk, sub0 - SG, parity); parity ^= 1; ++next_chunk; }
             while (next_chunk < upto) { issue(next_chunk); finish(next_chunk, sub0 - SG, parity); parity ^= 1; ++next_chunk; }
@@ -506,35 +499,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4, 4))) voi
             for (int g = 0; g < SG; ++g) wcnt_s[g * 4 + w] = min(wcnt[g], S);
         }
         __syncthreads();                                            // lists complete; every stretch of the previous subgroup stored
-        // ---- selected indices of this subgroup: concatenate, truncate, wrap-pad (roipool3d_kernel.cu:139-157)
+        // ---- selected indices of this subgroup
         for (int g = 0; g < SG && sub0 + g < nb; ++g) {
             const size_t bm = (size_t)b * boxes_num + box0 + sub0 + g;
-            const uint16_t *lg = lists + g * 4 * S;
-            const int c0 = wcnt_s[g * 4 + 0], c1 = wcnt_s[g * 4 + 1], c2 = wcnt_s[g * 4 + 2], c3 = wcnt_s[g * 4 + 3];
-            const int cnt = min(c0 + c1 + c2 + c3, S);
+            const int cnt = roi_select(lists + g * 4 * S, wcnt_s + g * 4, S, Q, sel + g * S, pts_idx ? pts_idx + bm * S : nullptr);
             if (tid == 0) cnt_s[g] = cnt;
-            if (cnt == 0) {      // roipool3d_kernel.cu:147-149,181-183: flag the box, leave its rows untouched
-                if (tid == 0) empty_flag[bm] = 1;
-                if (pts_idx)
-                    for (int q = tid; q < S; q += 256) pts_idx[bm * S + q] = 0;
-                if (fill) {
-                    float4v *o = reinterpret_cast<float4v *>(pooled + bm * (size_t)S * row);
-                    const float4v zero = {0.f, 0.f, 0.f, 0.f};
-                    for (int q = tid; q < (S * row) >> 2; q += 256) o[q] = zero;
-                }
-                continue;
-            }
-            if (fill && tid == 0) empty_flag[bm] = 0;
-            for (int q = tid; q < S; q += 256) {
-                int t = q < cnt ? q : q % cnt;
-                int v;
-                if (t < c0) v = lg[t];
-                else if ((t -= c0) < c1) v = Q + lg[S + t];
-                else if ((t -= c1) < c2) v = 2 * Q + lg[2 * S + t];
-                else v = 3 * Q + lg[3 * S + (t - c2)];
-                sel[g * S + q] = v;
-                if (pts_idx) pts_idx[bm * S + q] = v;
-            }
+            if (cnt == 0) roi_empty_box(bm, S, row, fill, empty_flag, pts_idx, pooled);
+            else if (fill && tid == 0) empty_flag[bm] = 0;
         }
         for (int g = min(SG, nb - sub0); g < SG; ++g)
             if (tid == 0) cnt_s[g] = 0;
@@ -719,6 +690,7 @@ __global__ __launch_bounds__(256) void roipool3d_binned_kernel(int pts_num, int 
                                                                int32_t *__restrict__ pts_idx, int fill, int batch) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int row = 3 + feat_len;
+    __builtin_assume(((S * row) & 3) == 0);            // (roi_plan; roi_empty_box then has no tail)
     float *stage = reinterpret_cast<float *>(smem);                                 // 2 * CR * row
     int *sel = reinterpret_cast<int *>(stage + 2 * CR * row);                       // S
     int *G = sel + S;                                                               // S + (1 << shift)
@@ -803,15 +775,8 @@ __global__ __launch_bounds__(256) void roipool3d_binned_kernel(int pts_num, int 
     }
     __syncthreads();
     const int K = s_K, T = s_T;
-    if (K == 0) {      // roipool3d_kernel.cu:147-149,181-183: flag the box, leave its rows untouched
-        if (tid == 0) empty_flag[bm] = 1;
-        if (pts_idx)
-            for (int q = tid; q < S; q += 256) pts_idx[bm * S + q] = 0;
-        if (fill) {
-            float4v *o = reinterpret_cast<float4v *>(pooled + bm * (size_t)S * row);
-            const float4v zero = {0.f, 0.f, 0.f, 0.f};
-            for (int q = tid; q < (S * row) >> 2; q += 256) o[q] = zero;
-        }
+    if (K == 0) {
+        roi_empty_box(bm, S, row, fill, empty_flag, pts_idx, pooled);
         return;
     }
     if (fill && tid == 0) empty_flag[bm] = 0;
@@ -837,34 +802,11 @@ __global__ __launch_bounds__(256) void roipool3d_binned_kernel(int pts_num, int 
     __syncthreads();
     if (pts_idx)
         for (int q = tid; q < S; q += 256) pts_idx[bm * S + q] = sel[q];
-    // ---- copy: the S x (3+C) block through LDS in stretches of CR rows (see roipool3d_kernel's copy phase)
-    float *out = pooled + bm * (size_t)S * row;
-    const int half = tid >> 5, l32 = tid & 31, f4 = feat_len >> 2;
-    constexpr int RPH = CR / 8;
+    // ---- copy: the S x (3+C) block through LDS in stretches of CR rows
     for (int c0 = 0, it = 0; c0 < S; c0 += CR, ++it) {
-        float *st = stage + (it & 1) * CR * row;
-        const int nr = min(CR, S - c0);
-        float4v v[RPH];
-        float p3[RPH];
-#pragma unroll
-        for (int u = 0; u < RPH; ++u) {
-            const int src = sel[min(c0 + half * RPH + u, S - 1)];
-            if (l32 < f4) v[u] = reinterpret_cast<const float4v *>(pts_feature + (size_t)src * feat_len)[l32];
-            if (l32 < 3) p3[u] = xyz[(size_t)src * 3 + l32];
-        }
-#pragma unroll
-        for (int u = 0; u < RPH; ++u) {
-            const int r = half * RPH + u;
-            if (r < nr) {
-                if (l32 < f4) *reinterpret_cast<float4u *>(st + r * row + 3 + 4 * l32) = v[u];
-                if (l32 < 3) st[r * row + l32] = p3[u];
-            }
-        }
-        __syncthreads();
-        float4v *o4 = reinterpret_cast<float4v *>(out + (size_t)c0 * row);
-        const int units = (nr * row) >> 2;
-        for (int q = tid; q < units; q += 256)
-            __builtin_nontemporal_store(*reinterpret_cast<const float4v *>(st + 4 * q), o4 + q);
+        RoiStretch<CR> stretch;
+        stretch.gather(sel, c0, S, xyz, pts_feature, feat_len);
+        stretch.deposit_store(stage + (it & 1) * CR * row, pooled + bm * (size_t)S * row, c0, S, row);
     }
 }
 
@@ -882,10 +824,23 @@ __global__ __launch_bounds__(256) void pts_in_boxes3d_kernel(int boxes_num, int 
 
 }  // namespace ws3d
 
+// the environment knobs of the launcher, read once per process (A/B runs and the tests that force every kernel on small shapes)
+struct RoiEnv {
+    int binned;   // WS3D_ROI_BINNED  0: never the binned kernel; N > 0: from N points on (default 16384)
+    int bg;       // WS3D_ROI_BG      1 / 2 / 4: boxes per workgroup of the scanning kernel
+    int stage;    // WS3D_ROI_STAGE   0 / 16 / 32: rows per LDS stretch of the copy (0: the direct copy)
+    int pipe;     // WS3D_ROI_PIPE    0: never the pipe kernel; 1 / 2: boxes per pass
+};
+static int roi_knob(const char *name, int unset) { const char *v = getenv(name); return v ? atoi(v) : unset; }
+static const RoiEnv &roi_env() {
+    static const RoiEnv env = {roi_knob("WS3D_ROI_BINNED", -1), roi_knob("WS3D_ROI_BG", 0), roi_knob("WS3D_ROI_STAGE", -1), roi_knob("WS3D_ROI_PIPE", -1)};
+    return env;
+}
+
 // scenes the binned variant takes (bytes of its workspace, 0: not applicable): large enough that the grid pays, indices that fit
 // 256 buckets of <= 1024
 static size_t roi_binned_bytes(int batch_size, int pts_num) {
-    static const int env = getenv("WS3D_ROI_BINNED") ? atoi(getenv("WS3D_ROI_BINNED")) : -1;     // 0: off; N > 0: from N points on (A/B runs)
+    const int env = roi_env().binned;
     const int min_n = env > 0 ? env : 16384;      // c3 (16384 points, 100 boxes): +1 % of the step; c5 (65536, 512): 0.365 -> 0.265 ms
     if (env == 0 || pts_num < min_n || pts_num > 256 * 1024 || batch_size <= 0) return 0;
     return (size_t)batch_size * ws3d::roi_bin_scene_stride(pts_num);
@@ -893,83 +848,109 @@ static size_t roi_binned_bytes(int batch_size, int pts_num) {
 
 extern "C" size_t ws3d_roipool3d_workspace_bytes(int batch_size, int pts_num) { return roi_binned_bytes(batch_size, pts_num); }
 
+// What a call launches.  family 0: roipool3d_kernel<g, cr> (g boxes per workgroup), 1: roipool3d_pipe_kernel<g, cr> (g boxes per
+// pass), 2: roi_bin_kernel + roipool3d_binned_kernel<cr> (g = 1); grid 0: nothing to launch.
+struct RoiPlan { int family, g, cr, shift; unsigned grid; size_t lds; };
+enum { ROI_SCAN = 0, ROI_PIPE = 1, ROI_BINNED = 2 };
+
+// The one place that decides.  aligned16: pts_feature and pooled_features are 16-byte aligned; ws_bytes: bytes of a usable
+// (non-null, 16-byte aligned) workspace, else 0.  No HIP call.
+static int roi_plan(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num, bool aligned16, size_t ws_bytes,
+                    RoiPlan &p) {
+    using namespace ws3d;
+    p = RoiPlan{ROI_SCAN, 1, 0, 0, 0u, 0};
+    if (batch_size < 0 || pts_num < 0 || boxes_num < 0 || feature_in_len < 0 || sampled_pts_num <= 0) {
+        set_error("ws3d_roipool3d: invalid argument (B=%d N=%d M=%d C=%d S=%d)", batch_size, pts_num,
+                  boxes_num, feature_in_len, sampled_pts_num);
+        return WS3D_E_INVALID;
+    }
+    if (batch_size == 0 || boxes_num == 0) return WS3D_OK;
+    const RoiEnv &env = roi_env();
+    const int row = 3 + feature_in_len;
+    const size_t S = (size_t)sampled_pts_num;
+    // boxes per workgroup: sharing the scene scan among 4 boxes pays when that still leaves >= 2 workgroups per CU
+    p.g = ((long)batch_size * ((boxes_num + 3) / 4) >= 512 && sampled_pts_num <= 1024) ? 4 : 1;
+    if (env.bg == 1 || env.bg == 2 || env.bg == 4) p.g = env.bg;
+    // rows staged through LDS by the copy phase (the aligned-store path): what its layout needs, else the direct copy
+    p.cr = (feature_in_len >= 4 && (feature_in_len & 3) == 0 && feature_in_len <= 128 && ((long)sampled_pts_num * row) % 4 == 0 && aligned16) ? 32 : 0;
+    const bool stage_forced = env.stage == 16 || env.stage == 32;
+    if (p.cr && (env.stage == 0 || stage_forced)) p.cr = env.stage;
+    p.lds = sizeof(int) * ((((size_t)p.g * 4 + 1) * S + 3) & ~(size_t)3) + sizeof(float) * 2 * (size_t)p.cr * row;
+    p.grid = (unsigned)(((boxes_num + p.g - 1) / p.g) * batch_size);
+    if (p.lds > 150 * 1024 || batch_size > 65535) {
+        set_error("ws3d_roipool3d: sampled_pts_num=%d / batch=%d unsupported", sampled_pts_num, batch_size);
+        return WS3D_E_UNSUPPORTED;
+    }
+    // large scenes with a workspace: bin the scene once, every box tests the cells under its footprint only
+    const size_t need = roi_binned_bytes(batch_size, pts_num);
+    if (need > 0 && ws_bytes >= need && p.cr > 0 && (sampled_pts_num & 3) == 0 && sampled_pts_num <= 2048 &&
+        (long)batch_size * boxes_num < (1L << 31)) {
+        p.family = ROI_BINNED; p.g = 1; p.cr = 16;
+        while ((256 << p.shift) < pts_num) ++p.shift;
+        p.lds = sizeof(float) * 2 * (size_t)p.cr * row + sizeof(int) * (2 * S + ((size_t)1 << p.shift));
+        p.grid = (unsigned)((long)batch_size * boxes_num);
+        return WS3D_OK;
+    }
+    // large scenes, 4 boxes per workgroup: the variant that overlaps scan and copy inside the workgroup
+    const int quarter = (((pts_num + 3) / 4 + 63) / 64) * 64;
+    if (p.g == 4 && p.cr > 0 && env.pipe != 0 && quarter <= 65536 && (sampled_pts_num & 3) == 0 && pts_num >= 16 * 1024) {
+        p.family = ROI_PIPE; p.g = env.pipe == 1 ? 1 : 2;
+        if (!stage_forced) p.cr = 16;
+        p.lds = sizeof(float) * 2 * (size_t)p.cr * row + sizeof(int) * (size_t)p.g * S + sizeof(uint16_t) * (size_t)p.g * 4 * S;
+    }
+    return WS3D_OK;
+}
+
+extern "C" int ws3d_roipool3d_plan(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num, int aligned16,
+                                   size_t workspace_bytes) {
+    RoiPlan p;
+    if (int rc = roi_plan(batch_size, pts_num, boxes_num, feature_in_len, sampled_pts_num, aligned16 != 0, workspace_bytes, p)) return rc;
+    return p.grid ? 1000 * p.family + 100 * p.g + p.cr : 0;
+}
+
+// scanning and pipe kernels share one signature
+typedef void (*RoiKernel)(int, int, int, int, const float *, const float *, const float *, float *, int32_t *, int32_t *, int, int);
+static RoiKernel roi_kernel(const RoiPlan &p) {
+    using namespace ws3d;
+    switch (1000 * p.family + 100 * p.g + p.cr) {
+        case 100: return roipool3d_kernel<1, 0>;   case 116: return roipool3d_kernel<1, 16>;   case 132: return roipool3d_kernel<1, 32>;
+        case 200: return roipool3d_kernel<2, 0>;   case 216: return roipool3d_kernel<2, 16>;   case 232: return roipool3d_kernel<2, 32>;
+        case 400: return roipool3d_kernel<4, 0>;   case 416: return roipool3d_kernel<4, 16>;   case 432: return roipool3d_kernel<4, 32>;
+        case 1116: return roipool3d_pipe_kernel<1, 16>;   case 1132: return roipool3d_pipe_kernel<1, 32>;
+        case 1216: return roipool3d_pipe_kernel<2, 16>;   case 1232: return roipool3d_pipe_kernel<2, 32>;
+    }
+    return nullptr;
+}
+
 static int roipool3d_launch(int batch_size, int pts_num, int boxes_num, int feature_in_len,
                             int sampled_pts_num, const float *xyz, const float *boxes3d,
                             const float *pts_feature, float *pooled_features,
                             int32_t *pooled_empty_flag, int32_t *pts_idx, int fill, ws3d_stream_t stream,
                             void *workspace = nullptr, size_t workspace_bytes = 0) {
     using namespace ws3d;
-    if (batch_size < 0 || pts_num < 0 || boxes_num < 0 || feature_in_len < 0 || sampled_pts_num <= 0 ||
-        !xyz || !boxes3d || (!pts_feature && feature_in_len > 0) || !pooled_features || !pooled_empty_flag) {
+    if (!xyz || !boxes3d || (!pts_feature && feature_in_len > 0) || !pooled_features || !pooled_empty_flag) {
         set_error("ws3d_roipool3d: invalid argument (B=%d N=%d M=%d C=%d S=%d)", batch_size, pts_num,
                   boxes_num, feature_in_len, sampled_pts_num);
         return WS3D_E_INVALID;
     }
-    if (batch_size == 0 || boxes_num == 0) return WS3D_OK;
-    // boxes per workgroup: sharing the scene scan among 4 boxes pays when that still leaves >= 2
-    // workgroups per CU (WS3D_ROI_BG overrides for A/B runs)
-    static const int bg_env = getenv("WS3D_ROI_BG") ? atoi(getenv("WS3D_ROI_BG")) : 0;
-    static const int cr_env = getenv("WS3D_ROI_STAGE") ? atoi(getenv("WS3D_ROI_STAGE")) : -1;   // 0 / 16 / 32: A/B runs
-    int bg = ((long)batch_size * ((boxes_num + 3) / 4) >= 512 && sampled_pts_num <= 1024) ? 4 : 1;
-    if (bg_env == 1 || bg_env == 2 || bg_env == 4) bg = bg_env;
-    const int row = 3 + feature_in_len;
-    // rows staged through LDS by the copy phase (the aligned-store path): what its layout needs, else the direct copy
-    int cr = (feature_in_len >= 4 && (feature_in_len & 3) == 0 && feature_in_len <= 128 && ((long)sampled_pts_num * row) % 4 == 0 &&
-              ((reinterpret_cast<uintptr_t>(pts_feature) | reinterpret_cast<uintptr_t>(pooled_features)) & 15) == 0) ? 32 : 0;
-    if (cr && (cr_env == 0 || cr_env == 16 || cr_env == 32)) cr = cr_env;
-    const size_t lists_ints = ((size_t)(bg * 4 + 1) * (size_t)sampled_pts_num + 3) & ~(size_t)3;
-    const size_t smem = sizeof(int) * lists_ints + sizeof(float) * 2 * (size_t)cr * row;
-    if (smem > 150 * 1024 || batch_size > 65535) {
-        set_error("ws3d_roipool3d: sampled_pts_num=%d / batch=%d unsupported", sampled_pts_num, batch_size);
-        return WS3D_E_UNSUPPORTED;
-    }
-    // large scenes with a workspace: bin the scene once, every box tests the cells under its footprint only
-    const size_t need = roi_binned_bytes(batch_size, pts_num);
-    if (workspace && need > 0 && workspace_bytes >= need && cr > 0 && (sampled_pts_num & 3) == 0 && sampled_pts_num <= 2048 &&
-        (long)batch_size * boxes_num < (1L << 31) && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0) {
-        int shift = 0;
-        while ((256 << shift) < pts_num) ++shift;
-        const int crb = 16;
-        const size_t lds = sizeof(float) * 2 * (size_t)crb * row + sizeof(int) * ((size_t)2 * sampled_pts_num + ((size_t)1 << shift));
+    RoiPlan p;
+    const bool aligned16 = ((reinterpret_cast<uintptr_t>(pts_feature) | reinterpret_cast<uintptr_t>(pooled_features)) & 15) == 0;
+    const bool ws_ok = workspace && (reinterpret_cast<uintptr_t>(workspace) & 15) == 0;
+    if (int rc = roi_plan(batch_size, pts_num, boxes_num, feature_in_len, sampled_pts_num, aligned16, ws_ok ? workspace_bytes : 0, p)) return rc;
+    if (p.grid == 0) return WS3D_OK;
+    if (p.family == ROI_BINNED) {
         hipLaunchKernelGGL(roi_bin_kernel, dim3(roi_chunks(pts_num), batch_size), dim3(1024), 0, as_stream(stream), pts_num, boxes_num, xyz, boxes3d,
                            reinterpret_cast<char *>(workspace));
-        if (int rc = raise_lds_cap((const void *)roipool3d_binned_kernel<16>, lds, "ws3d_roipool3d")) return rc;
-        hipLaunchKernelGGL((roipool3d_binned_kernel<16>), dim3((unsigned)((long)batch_size * boxes_num)), dim3(256), lds, as_stream(stream),
-                           pts_num, boxes_num, feature_in_len, sampled_pts_num, shift, xyz, reinterpret_cast<const char *>(workspace), boxes3d,
+        if (int rc = raise_lds_cap((const void *)roipool3d_binned_kernel<16>, p.lds, "ws3d_roipool3d")) return rc;
+        hipLaunchKernelGGL((roipool3d_binned_kernel<16>), dim3(p.grid), dim3(256), p.lds, as_stream(stream),
+                           pts_num, boxes_num, feature_in_len, sampled_pts_num, p.shift, xyz, reinterpret_cast<const char *>(workspace), boxes3d,
                            pts_feature, pooled_features, pooled_empty_flag, pts_idx, fill, batch_size);
         return check_launch("ws3d_roipool3d(binned)");
     }
-    // large scenes, 4 boxes per workgroup: the variant that overlaps scan and copy inside the workgroup
-    static const int pipe_env = getenv("WS3D_ROI_PIPE") ? atoi(getenv("WS3D_ROI_PIPE")) : -1;   // 0: off; 1 / 2: boxes per pass
-    const int quarter = (((pts_num + 3) / 4 + 63) / 64) * 64;
-    if (bg == 4 && cr > 0 && pipe_env != 0 && quarter <= 65536 && (sampled_pts_num & 3) == 0 && pts_num >= 16 * 1024) {
-        const int sg = pipe_env == 1 ? 1 : 2;
-        if (cr_env != 16 && cr_env != 32) cr = 16;
-        const size_t pm = sizeof(float) * 2 * (size_t)cr * row + sizeof(int) * (size_t)sg * sampled_pts_num +
-                          sizeof(uint16_t) * (size_t)sg * 4 * sampled_pts_num;
-#define WS3D_ROI_PIPE_LAUNCH(SGV, CRV)                                                                                            \
-        {                                                                                                                         \
-            if (int rc = raise_lds_cap((const void *)roipool3d_pipe_kernel<SGV, CRV>, pm, "ws3d_roipool3d")) return rc;            \
-            hipLaunchKernelGGL((roipool3d_pipe_kernel<SGV, CRV>), dim3((unsigned)(((boxes_num + 3) / 4) * batch_size)), dim3(256), pm, as_stream(stream), \
-                               pts_num, boxes_num, feature_in_len, sampled_pts_num, xyz, boxes3d, pts_feature, pooled_features,   \
-                               pooled_empty_flag, pts_idx, fill, batch_size);                                                                 \
-        }
-        if (sg == 1) { if (cr == 16) WS3D_ROI_PIPE_LAUNCH(1, 16) else WS3D_ROI_PIPE_LAUNCH(1, 32) }
-        else { if (cr == 16) WS3D_ROI_PIPE_LAUNCH(2, 16) else WS3D_ROI_PIPE_LAUNCH(2, 32) }
-#undef WS3D_ROI_PIPE_LAUNCH
-        return check_launch("ws3d_roipool3d");
-    }
-#define WS3D_ROI_LAUNCH(BGV, CRV)                                                                                  \
-    {                                                                                                              \
-        if (int rc = raise_lds_cap((const void *)roipool3d_kernel<BGV, CRV>, smem, "ws3d_roipool3d")) return rc;   \
-        hipLaunchKernelGGL((roipool3d_kernel<BGV, CRV>), dim3((unsigned)(((boxes_num + BGV - 1) / BGV) * batch_size)), dim3(256), smem, \
-                           as_stream(stream), pts_num, boxes_num, feature_in_len, sampled_pts_num, xyz, boxes3d,   \
-                           pts_feature, pooled_features, pooled_empty_flag, pts_idx, fill, batch_size);                        \
-    }
-#define WS3D_ROI_LAUNCH_BG(CRV) { if (bg == 4) WS3D_ROI_LAUNCH(4, CRV) else if (bg == 2) WS3D_ROI_LAUNCH(2, CRV) else WS3D_ROI_LAUNCH(1, CRV) }
-    if (cr == 32) WS3D_ROI_LAUNCH_BG(32) else if (cr == 16) WS3D_ROI_LAUNCH_BG(16) else WS3D_ROI_LAUNCH_BG(0)
-#undef WS3D_ROI_LAUNCH_BG
-#undef WS3D_ROI_LAUNCH
+    const RoiKernel kernel = roi_kernel(p);
+    if (int rc = raise_lds_cap((const void *)kernel, p.lds, "ws3d_roipool3d")) return rc;
+    hipLaunchKernelGGL(kernel, dim3(p.grid), dim3(256), p.lds, as_stream(stream), pts_num, boxes_num, feature_in_len, sampled_pts_num, xyz,
+                       boxes3d, pts_feature, pooled_features, pooled_empty_flag, pts_idx, fill, batch_size);
     return check_launch("ws3d_roipool3d");
 }
 
