@@ -840,6 +840,17 @@ WS3D_API int ws3d_rpn_loss(int rows, int bins, double loc_scope, double loc_bin_
 WS3D_API int ws3d_roipool3d_plan(int batch_size, int pts_num, int boxes_num, int feature_in_len, int sampled_pts_num, int aligned16,
                                  size_t workspace_bytes);
 
+/* What ws3d_ball_query / _fill / _pairs / _pairs2 / ws3d_query_and_group / _nlc would launch for these sizes, without launching it.
+ * fused: the query_and_group entries (c feature channels, nlc: channels-last); flavour: what the sort entry points noted for the
+ * binned copy (1: ws3d_sort_points_grid / a "grid" job, 0: any other binned copy, -1: none); pairs: the compact pairs are wanted;
+ * scales: 1, or 2 for ws3d_ball_query_pairs2 (nsample = the longer of its two lists); wide_nw: the value of ws3d_tune key 5.
+ * plan[0..7] = family (0: ball_query_kernel, 1: ball_query_sorted_kernel, 2: ball_query_grid_kernel, 3: ball_query_grid_coop_kernel),
+ * bits of a list index in LDS (16 | 32), FUSED, waves per workgroup, workgroups per tile of 64 centres (grid z), dynamic LDS bytes,
+ * grid x, grid y; all zero when there is nothing to launch (b == 0 or m == 0) or the sizes are refused.  Returns WS3D_OK or the
+ * launcher's error code.  The launchers decide through the same function.  No HIP call.  (tests/test_ballquery_plan.py) */
+WS3D_API int ws3d_ball_query_plan(int b, int n, int m, int c, int nsample, int fused, int nlc, int flavour, int pairs, int scales, int wide_nw,
+                                  int32_t *plan);
+
 #ifdef __cplusplus
 }
 #endif

@@ -224,3 +224,93 @@ ROI_VARIANT_SEEDS = [30, 31, 32, 33, 34, 60, 61]
 # (B, n, m, c, s, cfg) of test_roipool3d_bit_exact (default environment)
 ROI_BIT_EXACT_CASES = [(2, 2048, 24, 8, 64, 1), (2, 16384, 100, 128, 512, 3), (1, 4096, 40, 16, 512, 2), (1, 512, 8, 3, 16, 4),
                        (1, 65536, 64, 128, 512, 5), (1, 1000, 5, 1, 700, 6)]
+
+
+# ----------------------------------------------------------------------------- ball-query launch coverage
+# The shapes of the ball-query tests of tests/test_gpu_parity.py, kept here so that tests/test_ballquery_plan.py can ask the launcher's
+# plan (ws3d_ball_query_plan) on the CPU which search kernel each of their calls takes.
+# (B, N, M, r, ns, kind) of test_ball_query_and_group_bit_exact
+BQ_CASES = [
+    (2, 2048, 256, 0.5, 16, "lidar"), (2, 4096, 300, 1.0, 32, "lidar"), (1, 1024, 128, 0.1, 64, "lidar"),
+    (3, 500, 77, 4.0, 8, "uniform"), (2, 16384, 4096, 0.1, 64, "lidar"), (1, 16384, 4096, 0.5, 32, "lidar"),
+    (1, 16384, 4096, 0.1, 16, "uniform"), (1, 4096, 1024, 2.0, 32, "lidar"), (1, 777, 5, 100.0, 64, "lidar"),
+    (1, 300, 129, 1.0, 3, "uniform"),
+]
+# (N, M, r, ns, kind), two scenes each: test_ball_query_sorted_slab_equals_bruteforce, test_ball_query_grid_one_wave_per_centre_dense_lists
+BQ_SLAB_CASES = [(16384, 4096, 0.1, 64, "lidar"), (16384, 1024, 0.5, 32, "uniform"), (4096, 1024, 1.0, 16, "lidar"), (2048, 300, 50.0, 8, "lidar"),
+                 (8192, 500, 0.3, 5, "dups")]
+BQ_DENSE_CASES = [(16384, 4096, 0.5, 32, "hdl64"), (16384, 4096, 0.1, 16, "hdl64"), (16384, 4096, 0.1, 64, "hdl64"),
+                  (4096, 1024, 1.0, 32, "hdl64"), (4096, 1024, 0.5, 16, "hdl64"), (16384, 512, 2.5, 64, "hdl64"),
+                  (16384, 777, 0.4, 32, "clump"), (16384, 300, 60.0, 32, "hdl64"), (8192, 500, 0.3, 5, "dups"),
+                  (16384, 2048, 0.5, 1, "hdl64"), (16384, 1000, 0.5, 33, "narrow")]
+# (B, N, M, r, ns, kind, grid, misalign) of test_query_and_group_one_feature_channel_with_lists
+BQ_ONE_CHANNEL_CASES = [
+    (2, 16384, 4096, 0.1, 64, "hdl64", True, False), (1, 16384, 4096, 0.5, 32, "hdl64", True, False), (2, 4096, 1000, 0.5, 16, "lidar", True, False),
+    (1, 2048, 333, 1.0, 12, "lidar", True, False), (1, 2048, 333, 1.0, 12, "lidar", False, False), (2, 3000, 257, 0.8, 20, "uniform", True, True),
+    (1, 900, 70, 2.0, 8, "lidar", None, False), (1, 4096, 1024, 0.5, 6, "lidar", True, False)]
+# (N, M, radii, nss, kind), eight scenes each: test_ball_query_pairs2_on_eight_waves_per_tile
+BQ_PAIRS2_NW8_CASES = [(16384, 4096, (0.1, 0.5), (16, 32), "hdl64"), (4096, 1024, (0.5, 1.0), (16, 32), "hdl64"),
+                       (4096, 1000, (1.0, 2.0), (16, 32), "lidar"), (2048, 64, (2.0, 4.0), (8, 64), "lidar")]
+# (B, N, M, r, ns) of test_ball_query_fine_grid_one_lane_per_centre: lists longer than the 64 entries the one-wave-per-centre kernel
+# takes, on a fine-grid buffer -> ball_query_grid_kernel.  M = 70: a ragged second tile; B = 8 / 3: the XCD-aware and the plain tile
+# decode; r = 60 on 4096 points: every point a candidate, more than the grid walk accepts (BQS_MAX_SLAB = 3072) -> the ordered scan.
+BQ_LANE_CASES = [(3, 2048, 70, 0.5, 72), (3, 2048, 70, 0.5, 128), (8, 2048, 70, 0.5, 72), (8, 2048, 70, 0.5, 128), (1, 4096, 70, 60.0, 72)]
+BQ_FLAVOUR_NS = (32, 72)            # test_ball_query_binned_buffer_of_another_flavour_on_a_noted_address (1 scene, 16384 -> 300)
+# (B, N, M, r, ns, C) of test_ball_query_lists_of_32_bit_indices: more than 65536 points, no binned copy -> ball_query_kernel<int32_t, *>
+BQ_WIDE_INDEX_CASE = (1, 65600, 70, 1.0, 8, 4)
+# (B, N, M, r, ns) of test_ball_query_on_more_tiles_than_the_wide_launch_takes: 2048 tiles of 64 centres and more -> four waves per tile
+# (ball_query_grid_coop_kernel<*, 4>), with the XCD-aware (B % 8 == 0) and the plain tile decode
+BQ_MANY_SCENES_CASES = [(2048, 128, 64, 4.0, 16), (2049, 128, 64, 4.0, 16)]
+
+
+def bq_plan_calls():
+    """[(b, n, m, c, nsample, fused, nlc, flavour, pairs, scales, wide_nw)]: the arguments of ws3d_ball_query_plan for the searches the
+    tests above launch (flavour 1: a fine-grid buffer, 0: x slabs, -1: no binned copy)"""
+    calls = []
+
+    def lists(b, n, m, ns, flavour, pairs=0, scales=1, nw=0):
+        calls.append((b, n, m, 0, ns, 0, 0, flavour, pairs, scales, nw))
+
+    def fused(b, n, m, c, ns, flavour, nlc=0):
+        calls.append((b, n, m, c, ns, 1, nlc, flavour, 0, 1, 0))
+
+    def auto(n):                                       # pn2_ops bins the scene itself where compat.sort_points_x takes it
+        return 1 if 2048 <= n <= 16384 else -1
+
+    for B, N, M, r, ns, kind in BQ_CASES:
+        lists(B, N, M, ns, auto(N))
+        for c in (5, 0):
+            fused(B, N, M, c, ns, auto(N))
+    for N, M, r, ns, kind in BQ_SLAB_CASES:
+        for flavour in (1, 0, -1):
+            lists(2, N, M, ns, flavour)
+    for N, M, r, ns, kind in BQ_DENSE_CASES:
+        lists(2, N, M, ns, 1)
+        lists(2, N, M, ns, 1, pairs=1)
+        lists(2, N, M, max(ns, 16 if ns != 16 else 32), 1, pairs=1, scales=2)
+        lists(2, N, M, ns, -1)
+        fused(2, N, M, 8, ns, 1, nlc=1)
+    for ns in BQ_FLAVOUR_NS:
+        lists(1, 16384, 300, ns, 1)
+    for B, N, M, r, ns, kind, grid, misalign in BQ_ONE_CHANNEL_CASES:
+        fused(B, N, M, 1, ns, {True: 1, False: 0, None: -1}[grid])
+        lists(B, N, M, ns, auto(N))
+    for N, M, radii, nss, kind in BQ_PAIRS2_NW8_CASES:
+        for nw in (0, 8):
+            lists(8, N, M, max(nss), 1, pairs=1, scales=2, nw=nw)
+        if N == 2048:
+            fused(8, N, M, 8, nss[0], 1, nlc=1)
+    for B, N, M, r, ns in BQ_LANE_CASES:
+        lists(B, N, M, ns, 1)
+        fused(B, N, M, 1, ns, 1)
+        fused(B, N, M, 8, ns, 1, nlc=1)
+        if B == 3:
+            lists(B, N, M, 32, 1, pairs=1, scales=2, nw=8)
+    B, N, M, r, ns, C = BQ_WIDE_INDEX_CASE
+    lists(B, N, M, ns, -1)
+    fused(B, N, M, C, ns, -1)
+    for B, N, M, r, ns in BQ_MANY_SCENES_CASES:
+        lists(B, N, M, ns, 1)
+        lists(B, N, M, 32, 1, pairs=1, scales=2)
+        fused(B, N, M, 1, ns, 1)
+    return calls

@@ -242,16 +242,8 @@ def test_fps_temp_contract(ops, oracle):
 
 
 # ------------------------------------------------------------------------------- ball query / group
-BQ_CASES = [
-    # (B, N, M, r, ns, kind)
-    (2, 2048, 256, 0.5, 16, "lidar"), (2, 4096, 300, 1.0, 32, "lidar"), (1, 1024, 128, 0.1, 64, "lidar"),
-    (3, 500, 77, 4.0, 8, "uniform"), (2, 16384, 4096, 0.1, 64, "lidar"), (1, 16384, 4096, 0.5, 32, "lidar"),
-    (1, 16384, 4096, 0.1, 16, "uniform"), (1, 4096, 1024, 2.0, 32, "lidar"), (1, 777, 5, 100.0, 64, "lidar"),
-    (1, 300, 129, 1.0, 3, "uniform"),
-]
-
-
-@pytest.mark.parametrize("B,N,M,r,ns,kind", BQ_CASES)
+# (the shapes of the ball-query tests live in tests/helpers.py: tests/test_ballquery_plan.py checks on the CPU that they reach every search kernel)
+@pytest.mark.parametrize("B,N,M,r,ns,kind", H.BQ_CASES)
 def test_ball_query_and_group_bit_exact(ops, oracle, B, N, M, r, ns, kind):
     pc = synth.make_batch(kind, B, N, 21)
     xyz = pc[:, :, :3].copy()
@@ -281,9 +273,7 @@ def test_ball_query_and_group_bit_exact(ops, oracle, B, N, M, r, ns, kind):
     np.testing.assert_array_equal(host(qg2(dev(xyz), dev(new_xyz), dev(feats))), ref_g)
 
 
-@pytest.mark.parametrize("N,M,r,ns,kind", [(16384, 4096, 0.1, 64, "lidar"), (16384, 1024, 0.5, 32, "uniform"),
-                                          (4096, 1024, 1.0, 16, "lidar"), (2048, 300, 50.0, 8, "lidar"),
-                                          (8192, 500, 0.3, 5, "dups")])
+@pytest.mark.parametrize("N,M,r,ns,kind", H.BQ_SLAB_CASES)
 def test_ball_query_sorted_slab_equals_bruteforce(ops, oracle, N, M, r, ns, kind):
     """the x-sorted slab path, the LDS-tiled brute-force path and the oracle agree bit for bit,
     including slabs longer than the fallback threshold (r=50) and heavy duplication"""
@@ -342,10 +332,7 @@ def test_ball_query_sorted_slab_equals_bruteforce(ops, oracle, N, M, r, ns, kind
     np.testing.assert_array_equal(host(bb), ref)
 
 
-@pytest.mark.parametrize("N,M,r,ns,kind", [(16384, 4096, 0.5, 32, "hdl64"), (16384, 4096, 0.1, 16, "hdl64"), (16384, 4096, 0.1, 64, "hdl64"),
-                                          (4096, 1024, 1.0, 32, "hdl64"), (4096, 1024, 0.5, 16, "hdl64"), (16384, 512, 2.5, 64, "hdl64"),
-                                          (16384, 777, 0.4, 32, "clump"), (16384, 300, 60.0, 32, "hdl64"), (8192, 500, 0.3, 5, "dups"),
-                                          (16384, 2048, 0.5, 1, "hdl64"), (16384, 1000, 0.5, 33, "narrow")])
+@pytest.mark.parametrize("N,M,r,ns,kind", H.BQ_DENSE_CASES)
 def test_ball_query_grid_one_wave_per_centre_dense_lists(ops, oracle, N, M, r, ns, kind):
     """the fine-grid ball query with one WAVE per centre (threshold selection of the nsample smallest indices) on clouds with KITTI's
     density -- tens to hundreds of hits per ball -- against the oracle: lists bit-exact, through the plain and the fill entry, the
@@ -424,12 +411,138 @@ def test_ball_query_binned_buffer_of_another_flavour_on_a_noted_address(ops, ora
     xyz = synth.hdl64_cloud(16384, 44)[None, :, :3].copy()
     cidx = oracle.furthest_point_sample(xyz, 300)
     new_xyz = np.stack([xyz[0][cidx[0]]])
-    ref = oracle.ball_query(0.5, 32, xyz, new_xyz)
     x, c = dev(xyz), dev(new_xyz)
     grid = ops.c.sort_points_x(x, grid=True)
     slabs = ops.c.sort_points_x(x, grid=False)
     grid.copy_(slabs)
-    np.testing.assert_array_equal(host(ops.c.ball_query_lists(0.5, 32, x, c, grid)), ref)
+    for ns in H.BQ_FLAVOUR_NS:          # 32: one wave per centre; 72: one lane per centre (ball_query_grid_kernel reads the header too)
+        np.testing.assert_array_equal(host(ops.c.ball_query_lists(0.5, ns, x, c, grid)), oracle.ball_query(0.5, ns, xyz, new_xyz))
+
+
+def _grouped_ref(oracle, xyz, new_xyz, feats_ncl, ref_idx):
+    """the reference composition (pointnet2_utils.py:241-264): (B, 3 + C, M, ns) from the oracle's lists"""
+    xyz_t = np.ascontiguousarray(np.transpose(xyz, (0, 2, 1)))
+    return np.concatenate([oracle.grouping_operation(xyz_t, ref_idx) - np.transpose(new_xyz, (0, 2, 1))[..., None],
+                           oracle.grouping_operation(feats_ncl, ref_idx)], 1)
+
+
+def _pair_set(rowc, rowsrc, total):
+    """the compact (centre, source) table as a sorted (total, 2) array: its row order depends on an atomic"""
+    t = int(total.item())
+    pairs = np.stack([host(rowc[:t]), host(rowsrc[:t])], 1)
+    return pairs[np.lexsort((pairs[:, 1], pairs[:, 0]))]
+
+
+def _want_pairs(ref):
+    """the distinct entries of every list (the padding repeats the first; a centre without a hit pairs with point 0), sorted"""
+    flat = ref.reshape(-1, ref.shape[2])
+    distinct = (np.diff(flat, axis=1) > 0).sum(1) + 1
+    keep = np.arange(flat.shape[1])[None, :] < distinct[:, None]
+    return np.stack([np.broadcast_to(np.arange(flat.shape[0])[:, None], flat.shape)[keep], flat[keep]], 1)
+
+
+@pytest.fixture(scope="module")
+def bq_lane_scenes(oracle):
+    """(xyz, new_xyz, 1-channel features, 8-channel rows) per (B, N, M) of H.BQ_LANE_CASES, computed once"""
+    out = {}
+    for B, N, M, r, ns in H.BQ_LANE_CASES:
+        if (B, N, M) not in out:
+            base = synth.hdl64_cloud(16384, 46)
+            pc = np.stack([base[b::B][:N] for b in range(B)])           # B interleaved sub-scans of one scan: KITTI's density pattern
+            xyz = np.ascontiguousarray(pc[:, :, :3])
+            cidx = oracle.furthest_point_sample(xyz, M)
+            rows = np.random.default_rng(8).standard_normal((B, N, 8)).astype(np.float32)
+            out[(B, N, M)] = (xyz, np.stack([xyz[b][cidx[b]] for b in range(B)]), np.ascontiguousarray(np.transpose(pc[:, :, 3:4], (0, 2, 1))), rows)
+    return out
+
+
+@pytest.mark.parametrize("B,N,M,r,ns", H.BQ_LANE_CASES)
+def test_ball_query_fine_grid_one_lane_per_centre(ops, oracle, bq_lane_scenes, B, N, M, r, ns):
+    """lists longer than 64 entries on a fine-grid buffer take ball_query_grid_kernel (one lane per centre, wave 0 searches): the oracle's
+    lists through the plain and the fill entry, the reference composition through both fused entries.  70 centres: a ragged second tile;
+    8 / 3 scenes: the XCD-aware and the plain tile decode; r = 60 on 4096 points: more candidates than the grid walk accepts -> the
+    ordered scan (tests/test_ballquery_plan.py: these shapes take that kernel)"""
+    xyz, new_xyz, feats, rows = bq_lane_scenes[(B, N, M)]
+    ref = oracle.ball_query(r, ns, xyz, new_xyz)
+    x, c = dev(xyz), dev(new_xyz)
+    grid = ops.c.sort_points_x(x, min_n=1, grid=True)
+    assert grid is not None
+    g = torch.zeros((B, M, ns), dtype=torch.int32, device="cuda")
+    ops.c.ball_query_wrapper(B, N, M, r, ns, c, x, g, grid)
+    np.testing.assert_array_equal(host(g), ref)
+    np.testing.assert_array_equal(host(ops.c.ball_query_lists(r, ns, x, c, grid)), ref)
+    nbr = torch.full((B, M, ns), -7, dtype=torch.int32, device="cuda")
+    out = torch.full((B, 4, M, ns), float("nan"), device="cuda")
+    ops.c.query_and_group(B, N, M, 1, r, ns, True, x, c, dev(feats), nbr, out, grid)
+    np.testing.assert_array_equal(host(nbr), ref)
+    np.testing.assert_array_equal(host(out), _grouped_ref(oracle, xyz, new_xyz, feats, ref))
+    gl = ops.c.query_and_group_nlc(r, ns, x, c, dev(rows), True, grid)
+    want = _grouped_ref(oracle, xyz, new_xyz, np.ascontiguousarray(np.transpose(rows, (0, 2, 1))), ref)
+    np.testing.assert_array_equal(host(gl), np.transpose(want, (0, 2, 3, 1)))
+    if B == 3 and ns == 72:
+        # while a three-scene fine-grid buffer is at hand: the two-scale launch on 8 waves per tile with the plain tile decode
+        prev = ops.c.tune("bq_wide_nw", 8)
+        try:
+            dual = ops.c.ball_query_pairs2((r, 2 * r), (16, 32), x, c, grid)
+        finally:
+            ops.c.tune("bq_wide_nw", prev)
+        assert dual is not None
+        for (lst, (rowc, rowsrc, total)), (r2, ns2) in zip(dual, ((r, 16), (2 * r, 32))):
+            ref2 = oracle.ball_query(r2, ns2, xyz, new_xyz)
+            np.testing.assert_array_equal(host(lst), ref2)
+            np.testing.assert_array_equal(_pair_set(rowc, rowsrc, total), _want_pairs(ref2))
+
+
+def test_ball_query_lists_of_32_bit_indices(ops, oracle):
+    """more than 65536 points (no binned copy takes them): ball_query_kernel<int32_t, *> holds its lists as 32-bit indices in LDS --
+    the oracle's lists, and the reference composition with 3 + 4 channels"""
+    B, N, M, r, ns, C = H.BQ_WIDE_INDEX_CASE
+    xyz = synth.hdl64_cloud(N, 47)[None, :, :3].copy()
+    # the points past 65535 form a clump of their own, away from the scan: the lists of a centre in it hold indices of 17 bits only
+    xyz[0, 65536:] = (np.array([200.0, 0.0, 30.0]) + np.random.default_rng(9).uniform(-0.3, 0.3, (N - 65536, 3))).astype(np.float32)
+    new_xyz = np.ascontiguousarray(xyz[:, N - 1 - 911 * np.arange(M)])          # centres spread over the scan, the last point among them
+    ref = oracle.ball_query(r, ns, xyz, new_xyz)
+    assert ref[0, 0].min() >= 65536 and len(set(ref[0, 0])) == ns
+    x, c = dev(xyz), dev(new_xyz)
+    assert ops.c.sort_points_x(x) is None
+    g = torch.zeros((B, M, ns), dtype=torch.int32, device="cuda")
+    ops.c.ball_query_wrapper(B, N, M, r, ns, c, x, g, None)
+    np.testing.assert_array_equal(host(g), ref)
+    feats = np.random.default_rng(9).standard_normal((B, C, N)).astype(np.float32)
+    nbr = torch.full((B, M, ns), -7, dtype=torch.int32, device="cuda")
+    out = torch.full((B, 3 + C, M, ns), float("nan"), device="cuda")
+    ops.c.query_and_group(B, N, M, C, r, ns, True, x, c, dev(feats), nbr, out, None)
+    np.testing.assert_array_equal(host(nbr), ref)
+    np.testing.assert_array_equal(host(out), _grouped_ref(oracle, xyz, new_xyz, feats, ref))
+
+
+@pytest.mark.parametrize("B,N,M,r,ns", H.BQ_MANY_SCENES_CASES)
+def test_ball_query_on_more_tiles_than_the_wide_launch_takes(ops, oracle, B, N, M, r, ns):
+    """2048 tiles of 64 centres and more: the one-wave-per-centre kernel on four waves per tile (ball_query_grid_coop_kernel<*, 4>, the
+    geometry of the c2 block), lists only, both scales in one launch and fused -- many small scenes, the smallest shape that gets there"""
+    base = synth.hdl64_cloud(16384, 48)
+    pick = np.random.default_rng(10).integers(0, 16384, (B, N))
+    xyz = np.ascontiguousarray(base[pick][:, :, :3])
+    feats = np.ascontiguousarray(np.transpose(base[pick][:, :, 3:4], (0, 2, 1)))
+    new_xyz = np.ascontiguousarray(xyz[:, ::2][:, :M])
+    ref = oracle.ball_query(r, ns, xyz, new_xyz)
+    x, c = dev(xyz), dev(new_xyz)
+    grid = ops.c.sort_points_x(x, min_n=1, grid=True)
+    assert grid is not None
+    g = torch.zeros((B, M, ns), dtype=torch.int32, device="cuda")
+    ops.c.ball_query_wrapper(B, N, M, r, ns, c, x, g, grid)
+    np.testing.assert_array_equal(host(g), ref)
+    dual = ops.c.ball_query_pairs2((r, 2 * r), (ns, 32), x, c, grid)
+    assert dual is not None
+    for (lst, (rowc, rowsrc, total)), (r2, ns2) in zip(dual, ((r, ns), (2 * r, 32))):
+        ref2 = oracle.ball_query(r2, ns2, xyz, new_xyz)
+        np.testing.assert_array_equal(host(lst), ref2)
+        np.testing.assert_array_equal(_pair_set(rowc, rowsrc, total), _want_pairs(ref2))
+    nbr = torch.full((B, M, ns), -7, dtype=torch.int32, device="cuda")
+    out = torch.full((B, 4, M, ns), float("nan"), device="cuda")
+    ops.c.query_and_group(B, N, M, 1, r, ns, True, x, c, dev(feats), nbr, out, grid)
+    np.testing.assert_array_equal(host(nbr), ref)
+    np.testing.assert_array_equal(host(out), _grouped_ref(oracle, xyz, new_xyz, feats, ref))
 
 
 def test_ball_query_no_hit_rows_untouched(ops, oracle):
@@ -2726,10 +2839,7 @@ def test_compact_and_dense_sharedmlps_give_the_same_network_outputs(ops):
         fastpath.COMPACT_MAX_FILL, fastpath.COMPACT_PAIRS, fastpath.PER_POINT_L1 = saved
 
 
-@pytest.mark.parametrize("B,N,M,r,ns,kind,grid,misalign", [
-    (2, 16384, 4096, 0.1, 64, "hdl64", True, False), (1, 16384, 4096, 0.5, 32, "hdl64", True, False), (2, 4096, 1000, 0.5, 16, "lidar", True, False),
-    (1, 2048, 333, 1.0, 12, "lidar", True, False), (1, 2048, 333, 1.0, 12, "lidar", False, False), (2, 3000, 257, 0.8, 20, "uniform", True, True),
-    (1, 900, 70, 2.0, 8, "lidar", None, False), (1, 4096, 1024, 0.5, 6, "lidar", True, False)])
+@pytest.mark.parametrize("B,N,M,r,ns,kind,grid,misalign", H.BQ_ONE_CHANNEL_CASES)
 def test_query_and_group_one_feature_channel_with_lists(ops, oracle, B, N, M, r, ns, kind, grid, misalign):
     """the (3 xyz + 1 feature channel) shape of the c2 block / the first SA level through ws3d_query_and_group with the lists written
     beside the grouped rows (round 6: four entries per lane as one 16-byte store, entry -> centre by a shift): list lengths that are
@@ -2763,8 +2873,7 @@ def test_query_and_group_one_feature_channel_with_lists(ops, oracle, B, N, M, r,
     np.testing.assert_array_equal(host(got), ref_idx)
 
 
-@pytest.mark.parametrize("N,M,radii,nss,kind", [(16384, 4096, (0.1, 0.5), (16, 32), "hdl64"), (4096, 1024, (0.5, 1.0), (16, 32), "hdl64"),
-                                                (4096, 1000, (1.0, 2.0), (16, 32), "lidar"), (2048, 64, (2.0, 4.0), (8, 64), "lidar")])
+@pytest.mark.parametrize("N,M,radii,nss,kind", H.BQ_PAIRS2_NW8_CASES)
 def test_ball_query_pairs2_on_eight_waves_per_tile(ops, oracle, N, M, radii, nss, kind):
     """ws3d_tune key 5 (round 6: Stage1Pipeline's throughput geometry): the two-scale search launch on 8 waves x 8 centres per tile instead of
     16 x 4 -- the oracle's lists, and the same SET of compact (centre, source) pairs with the same totals as the default launch"""
@@ -2794,6 +2903,15 @@ def test_ball_query_pairs2_on_eight_waves_per_tile(ops, oracle, N, M, radii, nss
         assert res[8][k][1] == res[0][k][1]
         np.testing.assert_array_equal(res[8][k][2], res[0][k][2])
     assert ops.c.tune("bq_wide_nw") == 0
+    if N == 2048:
+        # the fused emit behind the same search on these eight scenes (16 waves per tile, XCD-aware tile decode)
+        ns = nss[0]
+        feat = dev(np.random.default_rng(7).standard_normal((B, N, 8)).astype(np.float32))
+        gl = ops.c.query_and_group_nlc(radii[0], ns, x, c, feat, True, grid)
+        li = torch.from_numpy(res[0][0][0].astype(np.int64)).cuda().view(B, M * ns, 1)
+        want = torch.cat((torch.gather(x, 1, li.expand(B, M * ns, 3)).view(B, M, ns, 3) - c.unsqueeze(2),
+                          torch.gather(feat, 1, li.expand(B, M * ns, 8)).view(B, M, ns, 8)), dim=3)
+        assert torch.equal(gl, want)
 
 
 def test_ball_query_fill_equals_ball_query_on_a_cleared_tensor(ops):

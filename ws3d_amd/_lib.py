@@ -150,6 +150,7 @@ SIGNATURES = {
     "ws3d_rpn_loss_workspace_bytes": (_sz, [_i]),
     "ws3d_rpn_loss": (_i, [_i, _i] + [C.c_double] * 6 + [_vp] * 8 + [_vp, _sz, _vp]),
     "ws3d_roipool3d_plan": (_i, [_i, _i, _i, _i, _i, _i, _sz]),
+    "ws3d_ball_query_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }
 
 

@@ -60,6 +60,49 @@ __device__ __forceinline__ void st4(float *p, const float4 v, const bool stream)
 }
 constexpr size_t STREAM_STORE_BYTES = (size_t)512 << 20;
 
+// ---- leaves of the epilogue
+typedef float f3v __attribute__((ext_vector_type(3)));
+typedef f3v f3u __attribute__((aligned(4)));
+
+// round 6: entry e of a tile's lists -> its centre by a shift where nsample is a power of two (ns_sh >= 0: every list length of the
+// network; a run-time integer division is ~20 VALU instructions per entry)
+__device__ __forceinline__ int bq_centre_of(const int e, const int ns_sh, const int nsample) { return ns_sh >= 0 ? e >> ns_sh : e / nsample; }
+
+// centred xyz of one neighbour: grouped_xyz -= new_xyz (pointnet2_utils.py:252).  X3: ONE 12-byte gather (global_load_dwordx3, 4-byte
+// aligned) instead of three dword gathers -- the emit is bound by the rate of uncoalesced L2 accesses (~1 lane per clock and CU), not by bytes
+template <bool X3>
+__device__ __forceinline__ f3v bq_centred(const float *__restrict__ xyz, const int id, const float4 ce) {
+    const float *p = xyz + (size_t)id * 3;
+    const f3v v = X3 ? f3v(*reinterpret_cast<const f3u *>(p)) : f3v{p[0], p[1], p[2]};
+    return f3v{v.x - ce.x, v.y - ce.y, v.z - ce.z};
+}
+
+// The lists of NC centres leave the chip, four entries per lane as 16-byte stores where nsample and the tensor's alignment allow (quads).
+// hit_only, the ball_query contract: rows without any hit are left untouched (ball_query_gpu.cu:29-44), or with `fill` (the _fill entry
+// point) written as zeros -- what the reference's callers get from their zero-initialised idx tensor.
+template <typename IDX, int NT, int NC>
+__device__ __forceinline__ void bq_write_lists(const int tid, const int m0, const int m, const int nsample, const int ns_sh, const bool quads,
+                                               int32_t *__restrict__ o /* the tile's first row */, const IDX *rows, const int rstride,
+                                               const int *cnt_s, const bool hit_only, const bool fill) {
+    const int total_e = NC * nsample;
+    if (quads) {
+        for (int q = tid; q < total_e / 4; q += NT) {
+            const int e = 4 * q, c = bq_centre_of(e, ns_sh, nsample);
+            if (m0 + c >= m) continue;
+            const IDX *r = rows + (size_t)c * rstride + (e - c * nsample);
+            if (!hit_only || cnt_s[c] > 0) *reinterpret_cast<int4 *>(o + e) = make_int4((int)r[0], (int)r[1], (int)r[2], (int)r[3]);
+            else if (fill) *reinterpret_cast<int4 *>(o + e) = make_int4(0, 0, 0, 0);
+        }
+        return;
+    }
+    for (int e = tid; e < total_e; e += NT) {
+        const int c = bq_centre_of(e, ns_sh, nsample), s = e - c * nsample;
+        if (m0 + c >= m) continue;
+        if (!hit_only || cnt_s[c] > 0) o[e] = (int32_t)rows[(size_t)c * rstride + s];
+        else if (fill) o[e] = 0;
+    }
+}
+
 // Shared epilogue: NC centres' padded neighbour rows (LDS) -> idx tensor and/or the fused
 // (B, 3+C, M, ns) grouped tensor, coalesced along (m, s).
 template <typename IDX, bool FUSED, int NT, int NC>
@@ -71,54 +114,19 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
                                         const bool pad_ready = false /* pad4 holds every centre's centred first hit already: no barrier in here */) {
     if (nbatch < 0) nbatch = (int)gridDim.y;      // scenes of the launch (the 1-D grid kernel passes it)
     const int total_e = NC * nsample;
-    // round 6: entry e -> (centre, sample) by a shift where nsample is a power of two (every list length of the network; a run-time
-    // integer division is ~20 VALU instructions per entry), and the lists leave the chip four entries per lane as 16-byte stores
     const int ns_sh = (nsample & (nsample - 1)) == 0 ? (int)__builtin_ctz((unsigned)nsample) : -1;
-    auto centre_of = [&](const int e) { return ns_sh >= 0 ? e >> ns_sh : e / nsample; };
+    auto centre_of = [&](const int e) { return bq_centre_of(e, ns_sh, nsample); };
     const bool idx_quads = (nsample & 3) == 0 && (reinterpret_cast<uintptr_t>(idx_out) & 15) == 0;
-    if (!FUSED) {
-        // ball_query contract: rows without any hit are left untouched (ball_query_gpu.cu:29-44); use_xyz bit 2 (the _fill entry
-        // point): such rows are written as zeros -- what the reference's callers get from their zero-initialised idx tensor
-        int32_t *o = idx_out + ((size_t)b * m + m0) * nsample;
-        const bool fill = (use_xyz & 4) != 0;
-        if (idx_quads) {
-            for (int q = tid; q < total_e / 4; q += NT) {
-                const int e = 4 * q, c = centre_of(e);
-                if (m0 + c >= m) continue;
-                const IDX *r = rows + (size_t)c * rstride + (e - c * nsample);
-                if (cnt_s[c] > 0) *reinterpret_cast<int4 *>(o + e) = make_int4((int)r[0], (int)r[1], (int)r[2], (int)r[3]);
-                else if (fill) *reinterpret_cast<int4 *>(o + e) = make_int4(0, 0, 0, 0);
-            }
-            return;
-        }
-        for (int e = tid; e < total_e; e += NT) {
-            const int c = centre_of(e), s = e - c * nsample;
-            if (m0 + c < m) {
-                if (cnt_s[c] > 0) o[e] = (int32_t)rows[(size_t)c * rstride + s];
-                else if (fill) o[e] = 0;
-            }
-        }
+    int32_t *const lists_row0 = idx_out ? idx_out + ((size_t)b * m + m0) * nsample : nullptr;
+    if (!FUSED) {                                            // (use_xyz bit 2: the _fill entry point)
+        bq_write_lists<IDX, NT, NC>(tid, m0, m, nsample, ns_sh, idx_quads, lists_row0, rows, rstride, cnt_s, true, (use_xyz & 4) != 0);
         return;
     }
     // (the 3 + 1 channel shape below writes the lists beside the grouped rows: it holds the four indices of a store in registers anyway)
     const bool lists_in_fast_path = !(use_xyz & 2) && c_feat == 1 && (use_xyz & 1) && gridDim.z == 1 && idx_quads &&
                                     (reinterpret_cast<uintptr_t>(out) & 15) == 0;
-    if (idx_out && blockIdx.z == 0 && !lists_in_fast_path) {
-        int32_t *o = idx_out + ((size_t)b * m + m0) * nsample;
-        if (idx_quads) {
-            for (int q = tid; q < total_e / 4; q += NT) {
-                const int e = 4 * q, c = centre_of(e);
-                if (m0 + c >= m) continue;
-                const IDX *r = rows + (size_t)c * rstride + (e - c * nsample);
-                *reinterpret_cast<int4 *>(o + e) = make_int4((int)r[0], (int)r[1], (int)r[2], (int)r[3]);
-            }
-        } else {
-            for (int e = tid; e < total_e; e += NT) {
-                const int c = centre_of(e), s = e - c * nsample;
-                if (m0 + c < m) o[e] = (int32_t)rows[(size_t)c * rstride + s];
-            }
-        }
-    }
+    if (idx_out && blockIdx.z == 0 && !lists_in_fast_path)
+        bq_write_lists<IDX, NT, NC>(tid, m0, m, nsample, ns_sh, idx_quads, lists_row0, rows, rstride, cnt_s, false, false);
     if (use_xyz & 2) {
         // channels-LAST output (b, m, nsample, 3 + C) from channels-last features (b, n, C): one
         // contiguous row per (centre, sample) -- the layout the row-major SharedMLP GEMMs consume
@@ -137,9 +145,8 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
                 const int c = e / nsample, s = e - c * nsample;
                 if (m0 + c >= m) continue;
                 const int id = (int)rows[(size_t)c * rstride + s];
-                const float4 ce = cen[c];
-                const float *p = xyz + (size_t)id * 3;
-                *reinterpret_cast<float4 *>(ob + (size_t)e * 4) = make_float4(p[0] - ce.x, p[1] - ce.y, p[2] - ce.z, fb[id]);
+                const f3v d = bq_centred<false>(xyz, id, cen[c]);
+                *reinterpret_cast<float4 *>(ob + (size_t)e * 4) = make_float4(d.x, d.y, d.z, fb[id]);
             }
         } else if ((c_feat & 3) == 0 && c_feat > 0 && (reinterpret_cast<uintptr_t>(fb) & 15) == 0) {
             typedef float f4v __attribute__((ext_vector_type(4)));
@@ -180,9 +187,8 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
                 const int id = (int)rows[(size_t)c * rstride + s];
                 float *o = ob + (size_t)e * row;
                 if (cx3) {
-                    const float4 ce = cen[c];
-                    const float *p = xyz + (size_t)id * 3;
-                    o[0] = p[0] - ce.x; o[1] = p[1] - ce.y; o[2] = p[2] - ce.z;
+                    const f3v d = bq_centred<false>(xyz, id, cen[c]);
+                    o[0] = d.x; o[1] = d.y; o[2] = d.z;
                 }
                 for (int ch = 0; ch < c_feat; ++ch) o[cx3 + ch] = fb[(size_t)id * c_feat + ch];
             }
@@ -209,10 +215,8 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
             // each with its own LDS round trip before the gather could issue), the gathers and stores take 32-bit offsets from scalar
             // bases, the streaming / plain store choice is made once per launch instead of once per store, and the lists go out here
             // (ws3d_query_and_group writes them too) as one 16-byte store per lane and group.
-            typedef float f3v __attribute__((ext_vector_type(3)));
-            typedef f3v f3u __attribute__((aligned(4)));
             const bool lists = idx_out && lists_in_fast_path;
-            int32_t *ib = lists ? idx_out + ((size_t)b * m + m0) * nsample : nullptr;
+            int32_t *ib = lists ? lists_row0 : nullptr;
             const char *xb = reinterpret_cast<const char *>(xyz), *fbb = reinterpret_cast<const char *>(fb);
             char *o0 = reinterpret_cast<char *>(ob), *o1 = reinterpret_cast<char *>(ob + plane), *o2 = reinterpret_cast<char *>(ob + 2 * plane),
                  *o3 = reinterpret_cast<char *>(ob + 3 * plane);
@@ -319,16 +323,11 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
             const int i0 = (int)r[0], i1 = (int)r[1], i2 = (int)r[2], i3 = (int)r[3];
             if (use_xyz && blockIdx.z == 0) {
                 const float4 ce = cen[c];
-                // ONE 12-byte gather per neighbour (global_load_dwordx3, 4-byte aligned) instead of three dword gathers: the
-                // emit is bound by the rate of uncoalesced L2 accesses (~1 lane per clock and CU), not by bytes
-                typedef float f3v __attribute__((ext_vector_type(3)));
-                typedef f3v f3u __attribute__((aligned(4)));
-                const f3v p0 = *reinterpret_cast<const f3u *>(xyz + (size_t)i0 * 3), p1 = *reinterpret_cast<const f3u *>(xyz + (size_t)i1 * 3),
-                          p2 = *reinterpret_cast<const f3u *>(xyz + (size_t)i2 * 3), p3 = *reinterpret_cast<const f3u *>(xyz + (size_t)i3 * 3);
-                // grouped_xyz -= new_xyz (pointnet2_utils.py:252)
-                *reinterpret_cast<float4 *>(ob + e) = make_float4(p0.x - ce.x, p1.x - ce.x, p2.x - ce.x, p3.x - ce.x);
-                *reinterpret_cast<float4 *>(ob + plane + e) = make_float4(p0.y - ce.y, p1.y - ce.y, p2.y - ce.y, p3.y - ce.y);
-                *reinterpret_cast<float4 *>(ob + 2 * plane + e) = make_float4(p0.z - ce.z, p1.z - ce.z, p2.z - ce.z, p3.z - ce.z);
+                const f3v d0 = bq_centred<true>(xyz, i0, ce), d1 = bq_centred<true>(xyz, i1, ce), d2 = bq_centred<true>(xyz, i2, ce),
+                          d3 = bq_centred<true>(xyz, i3, ce);
+                *reinterpret_cast<float4 *>(ob + e) = make_float4(d0.x, d1.x, d2.x, d3.x);
+                *reinterpret_cast<float4 *>(ob + plane + e) = make_float4(d0.y, d1.y, d2.y, d3.y);
+                *reinterpret_cast<float4 *>(ob + 2 * plane + e) = make_float4(d0.z, d1.z, d2.z, d3.z);
             }
             int ch = ch_lo;
             for (; ch + 4 <= ch_hi; ch += 4) {
@@ -353,14 +352,143 @@ __device__ __forceinline__ void bq_emit(int b, int tid, int m0, int n, int m, in
         if (m0 + c >= m) continue;
         const int id = (int)rows[(size_t)c * rstride + s];
         if (use_xyz && blockIdx.z == 0) {
-            const float4 ce = cen[c];
-            const float *p = xyz + (size_t)id * 3;
-            ob[e] = p[0] - ce.x;                 // grouped_xyz -= new_xyz (pointnet2_utils.py:252)
-            ob[plane + e] = p[1] - ce.y;
-            ob[2 * plane + e] = p[2] - ce.z;
+            const f3v d = bq_centred<false>(xyz, id, cen[c]);
+            ob[e] = d.x;
+            ob[plane + e] = d.y;
+            ob[2 * plane + e] = d.z;
         }
         for (int ch = ch_lo; ch < ch_hi; ++ch) ob[(size_t)(c_xyz + ch) * plane + e] = fb[(size_t)ch * n + id];
     }
+}
+
+// ----------------------------------------------------------------------------------------
+// Shared phases of the search kernels: the numerical contract -- which cells may hold a hit, first nsample by index, pad with the
+// first hit, a centre without a hit -- is spelled here, once each.
+constexpr int BQS_MAX_SLAB = 3072;    // candidates a lane walks before the ordered full scan takes over
+#ifndef BQS_UNROLL
+#define BQS_UNROLL 8
+#endif
+
+// blockIdx.x -> (scene, tile of 64 centres) of the 1-D grids.  XCD-aware where the scenes are a multiple of eight: workgroup g runs on
+// XCD g % 8 (observed dispatch order), so scene = (g / 8 / tiles) * 8 + g % 8 puts all tiles of a scene on ONE XCD -- its points and
+// features are pulled into one L2 instead of eight.
+__device__ __forceinline__ void bq_tile_of(const int nb, const int tiles, int &b, int &tile) {
+    if ((nb & 7) == 0) {
+        const int g = blockIdx.x, j = g >> 3;
+        b = (j / tiles) * 8 + (g & 7);
+        tile = j - (j / tiles) * tiles;
+    } else {
+        b = blockIdx.x / tiles;
+        tile = blockIdx.x - b * tiles;
+    }
+}
+
+// The decoded binned copy of scene b (binning.h): which flavour it holds is in its header.
+struct BqGrid { float xmin, inv_wx, zmin, inv_wz; int gx, gz; };      // the fine (x, z) grid's parameters
+struct BinView {
+    const float4 *sorted;        // n x {x, y, z, bits(index)}, counting-sorted by cell
+    BinHeader hdr;
+    const int *start;            // x slabs: BQS_CELLS + 1 cell starts
+    const uint16_t *start16;     // fine grid: gx * gz + 1 cell starts, row-major in z
+    const int *params;           // fine grid: zmin, 1 / cell depth, gz
+    __device__ __forceinline__ BinView(const char *__restrict__ ws, const int b, const int n) {
+        const char *base = ws + (size_t)b * bin_scene_stride(n);
+        sorted = reinterpret_cast<const float4 *>(base);
+        hdr = *reinterpret_cast<const BinHeader *>(base + (size_t)n * 16);
+        start = reinterpret_cast<const int *>(base + (size_t)n * 16 + sizeof(BinHeader));
+        start16 = reinterpret_cast<const uint16_t *>(start);
+        params = reinterpret_cast<const int *>(base + (size_t)n * 16 + sizeof(BinHeader) + GRID16_PARAMS);
+    }
+    __device__ __forceinline__ bool is_grid() const { return hdr.pad < 0; }
+    __device__ __forceinline__ BqGrid grid() const {
+        return BqGrid{hdr.xmin, hdr.inv_w, __int_as_float(params[0]), __int_as_float(params[1]), -hdr.pad, params[2]};
+    }
+};
+
+// The candidate window of a centre on the fine grid: columns ix0..ix1 of the rows iz0..iz1, one contiguous range of cells per row.
+// A hit has |fl(cx - px)| < r and |fl(cz - pz)| < r (each squared term alone is <= d2 under monotone rounding), i.e. px within
+// r (1 + 2^-23) of cx; the bounds are widened by 6e-7 (|c| + r) -- ten times the rounding of c -+ r -- and grid_coord is monotone, so
+// no cell holding a hit is skipped.
+struct BqWindow { int ix0, ix1, iz0, iz1; };
+__device__ __forceinline__ BqWindow bq_window(const BqGrid &g, const float cx, const float cz, const float rabs) {
+    const float sx = (fabsf(cx) + rabs) * 6e-7f, sz = (fabsf(cz) + rabs) * 6e-7f;
+    return BqWindow{grid_coord((cx - rabs) - sx, g.xmin, g.inv_wx, g.gx), grid_coord((cx + rabs) + sx, g.xmin, g.inv_wx, g.gx),
+                    grid_coord((cz - rabs) - sz, g.zmin, g.inv_wz, g.gz), grid_coord((cz + rabs) + sz, g.zmin, g.inv_wz, g.gz)};
+}
+// the one-lane kernels walk a window of at most BQS_MAX_SLAB candidates (the count stops once it is past that)
+__device__ __forceinline__ bool bq_window_walkable(const uint16_t *__restrict__ start16, const int gx, const BqWindow &w) {
+    int total = 0;
+    for (int iz = w.iz0; iz <= w.iz1 && total <= BQS_MAX_SLAB; ++iz)
+        total += (int)start16[iz * gx + w.ix1 + 1] - (int)start16[iz * gx + w.ix0];
+    return total <= BQS_MAX_SLAB;
+}
+
+// Candidates arrive in arbitrary order: the row keeps the nsample SMALLEST indices seen, ascending -- the reference's "first nsample
+// by index" set.
+__device__ __forceinline__ void bq_insert_smallest(uint16_t *row, int &cnt, const int nsample, const int id) {
+    if (cnt == nsample) {
+        if (id >= (int)row[nsample - 1]) return;
+        --cnt;
+    }
+    int pos = cnt;
+    while (pos > 0 && (int)row[pos - 1] > id) { row[pos] = row[pos - 1]; --pos; }
+    row[pos] = (uint16_t)id;
+    ++cnt;
+}
+// The walk over the candidates sorted[k .. ke), U entries per trip: the loads are independent of the tests, so the walk pays one memory
+// round trip per U candidates (clamped loads past the end are ignored).  |dx| >= r  =>  d2 >= r * r: the one-axis reject is exact.
+template <int U>
+__device__ __forceinline__ void bq_walk(const float4 *__restrict__ sorted, int k, const int ke, const float cx, const float cy, const float cz,
+                                        const float rabs, const float radius2, uint16_t *row, int &cnt, const int nsample) {
+    for (; k < ke; k += U) {
+        float4 p[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) p[u] = sorted[min(k + u, ke - 1)];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const float dx = cx - p[u].x;
+            if (k + u < ke && fabsf(dx) < rabs) {
+                const float d2 = sqdist3(dx, cy - p[u].y, cz - p[u].z);
+                if (d2 < radius2) bq_insert_smallest(row, cnt, nsample, __float_as_int(p[u].w));
+            }
+        }
+    }
+}
+
+// The reference's own loop (ball_query_gpu.cu:29-44): the scene in index order, stop at nsample hits.  One lane per centre, and one
+// wave per centre (64 points per step; returns the count, capped at nsample).  What serves pathological density and binned copies of
+// another flavour: slow, never wrong.
+__device__ __forceinline__ void bq_ordered_scan(const float *__restrict__ xyz, const int n, const float cx, const float cy, const float cz,
+                                                const float radius2, uint16_t *row, int &cnt, const int nsample) {
+    for (int q = 0; q < n && cnt < nsample; ++q) {
+        const float d2 = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]);
+        if (d2 < radius2) { row[cnt] = (uint16_t)q; ++cnt; }
+    }
+}
+__device__ __forceinline__ int bq_ordered_scan_wave(const int lane, const float *__restrict__ xyz, const int n, const float cx, const float cy,
+                                                    const float cz, const float radius2, uint16_t *row, const int nsample) {
+    int cnt = 0;
+    for (int q0 = 0; q0 < n && cnt < nsample; q0 += 64) {
+        const int q = q0 + lane;
+        bool hit = false;
+        if (q < n) hit = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]) < radius2;
+        const uint64_t mask = __ballot(hit);
+        const int pos = cnt + mbcnt(mask);
+        if (hit && pos < nsample) row[pos] = (uint16_t)q;
+        cnt += __popcll(mask);
+    }
+    return min(cnt, nsample);
+}
+
+// The tail of a row: entries past the centre's cnt hits repeat its first (smallest) one, zeros for a centre without a hit (only the
+// fused emit reads those), then the count is published.  `stride` lanes (this one is lane l of them) share the row; cnt_out NULL:
+// the caller publishes the count itself.
+template <typename IDX>
+__device__ __forceinline__ void bq_pad_row(IDX *row, const int cnt, const int nsample, const int l, const int stride, int *cnt_out,
+                                           const int published) {
+    const IDX first = cnt > 0 ? row[0] : (IDX)0;
+    for (int s = cnt + l; s < nsample; s += stride) row[s] = first;
+    if (l == 0 && cnt_out) *cnt_out = published;
 }
 
 constexpr int BQ_TILE = 256;  // points per wave-private LDS tile
@@ -453,9 +581,7 @@ __global__ __launch_bounds__(64 * BQ_NW) void ball_query_kernel(int n, int m, in
             const IDX *src = rows + (size_t)(ww * 64 + lane) * rstride;
             for (int s = 0; s < cw && total < nsample; ++s) row[total++] = src[s];
         }
-        const IDX first = total > 0 ? row[0] : (IDX)0;
-        for (int s = total; s < nsample; ++s) row[s] = first;
-        cnt_s[lane] = total;
+        bq_pad_row(row, total, nsample, 0, 1, &cnt_s[lane], total);
     }
     __syncthreads();
 
@@ -472,10 +598,6 @@ __global__ __launch_bounds__(64 * BQ_NW) void ball_query_kernel(int n, int m, in
 // distance test, padding and no-hit rules are unchanged, so the result is bit-identical to the
 // brute-force scan (and independent of the order inside a cell).  Slabs longer than
 // BQS_MAX_SLAB (pathological density) fall back to the ordered full scan for that lane.
-constexpr int BQS_MAX_SLAB = 3072;
-#ifndef BQS_UNROLL
-#define BQS_UNROLL 8
-#endif
 // one workgroup per scene: min/max of x, LDS histogram, exclusive scan, scatter
 __global__ __launch_bounds__(1024) void bin_points_x_kernel(int n, const float *__restrict__ xyz,
                                                             char *__restrict__ ws) {
@@ -564,10 +686,7 @@ __global__ __launch_bounds__(256) void ball_query_sorted_kernel(int n, int m, in
     const int mi = m0 + lane;
     const bool active = mi < m;
     xyz += (size_t)b * n * 3;
-    const char *base = ws + (size_t)b * bin_scene_stride(n);
-    const float4 *sorted = reinterpret_cast<const float4 *>(base);
-    const BinHeader hdr = *reinterpret_cast<const BinHeader *>(base + (size_t)n * 16);
-    const int *start = reinterpret_cast<const int *>(base + (size_t)n * 16 + sizeof(BinHeader));
+    const BinView bv(ws, b, n);
     new_xyz += (size_t)b * m * 3;
     float cx = 0.f, cy = 0.f, cz = 0.f;
     if (active) { cx = new_xyz[mi * 3 + 0]; cy = new_xyz[mi * 3 + 1]; cz = new_xyz[mi * 3 + 2]; }
@@ -578,81 +697,39 @@ __global__ __launch_bounds__(256) void ball_query_sorted_kernel(int n, int m, in
     const float rabs = fabsf(radius);
     uint16_t *row = part + (size_t)(w * 64 + lane) * rstride;
     int cnt = 0;
-    auto insert = [&](const int id) {  // keep the nsample smallest indices, ascending
-        if (cnt == nsample) {
-            if (id >= (int)row[nsample - 1]) return;
-            --cnt;
-        }
-        int pos = cnt;
-        while (pos > 0 && (int)row[pos - 1] > id) { row[pos] = row[pos - 1]; --pos; }
-        row[pos] = (uint16_t)id;
-        ++cnt;
-    };
 #ifdef WS3D_BQS_NO_SEARCH
-    if (active && w == 0) { for (int q = 0; q < 20; ++q) insert((mi * 7 + q * 13) % n); }
+    if (active && w == 0) { for (int q = 0; q < 20; ++q) bq_insert_smallest(row, cnt, nsample, (mi * 7 + q * 13) % n); }
     if (false) {
 #else
     if (active && cx == cx) {
 #endif
-        auto scan = [&](int k, const int ke) {
-            // BQS_UNROLL entries per trip: the loads are independent of the tests, so the walk pays one memory round trip
-            // per BQS_UNROLL candidates (clamped loads past the end are ignored)
-            for (; k < ke; k += BQS_UNROLL) {
-                float4 p[BQS_UNROLL];
-#pragma unroll
-                for (int u = 0; u < BQS_UNROLL; ++u) p[u] = sorted[min(k + u, ke - 1)];
-#pragma unroll
-                for (int u = 0; u < BQS_UNROLL; ++u) {
-                    const float dx = cx - p[u].x;
-                    if (k + u < ke && fabsf(dx) < rabs) {
-                        const float d2 = sqdist3(dx, cy - p[u].y, cz - p[u].z);
-                        if (d2 < radius2) insert(__float_as_int(p[u].w));
-                    }
-                }
-            }
-        };
         bool full_scan = false;
-        if (hdr.pad < 0) {
-            // fine (x, z) grid: a hit has |fl(cx - px)| < r and |fl(cz - pz)| < r (each squared term alone is <= d2 under
-            // monotone rounding), i.e. px within r (1 + 2^-23) of cx; the bounds are widened by 6e-7 (|c| + r) -- ten times
-            // the rounding of c -+ r -- and grid_coord is monotone, so no cell holding a hit is skipped.  Wave j takes
-            // the grid rows j, j + 4, ...: one contiguous range of cells per row.
-            const uint16_t *start16 = reinterpret_cast<const uint16_t *>(start);
-            const int *params = reinterpret_cast<const int *>(reinterpret_cast<const char *>(start) + GRID16_PARAMS);
-            const int gx = -hdr.pad, gz = params[2];
-            const float zmin = __int_as_float(params[0]), inv_wz = __int_as_float(params[1]);
-            const float sx = (fabsf(cx) + rabs) * 6e-7f, sz = (fabsf(cz) + rabs) * 6e-7f;
-            const int ix0 = grid_coord((cx - rabs) - sx, hdr.xmin, hdr.inv_w, gx), ix1 = grid_coord((cx + rabs) + sx, hdr.xmin, hdr.inv_w, gx);
-            const int iz0 = grid_coord((cz - rabs) - sz, zmin, inv_wz, gz), iz1 = grid_coord((cz + rabs) + sz, zmin, inv_wz, gz);
-            int total = 0;
-            for (int iz = iz0; iz <= iz1 && total <= BQS_MAX_SLAB; ++iz)
-                total += (int)start16[iz * gx + ix1 + 1] - (int)start16[iz * gx + ix0];
-            if (total <= BQS_MAX_SLAB) {
-                for (int iz = iz0 + w; iz <= iz1; iz += 4) scan((int)start16[iz * gx + ix0], (int)start16[iz * gx + ix1 + 1]);
+        if (bv.is_grid()) {
+            // fine (x, z) grid: wave j takes the window's rows j, j + 4, ...
+            const BqGrid g = bv.grid();
+            const BqWindow win = bq_window(g, cx, cz, rabs);
+            if (bq_window_walkable(bv.start16, g.gx, win)) {
+                for (int iz = win.iz0 + w; iz <= win.iz1; iz += 4)
+                    bq_walk<BQS_UNROLL>(bv.sorted, (int)bv.start16[iz * g.gx + win.ix0], (int)bv.start16[iz * g.gx + win.ix1 + 1], cx, cy, cz, rabs,
+                                        radius2, row, cnt, nsample);
             } else {
                 full_scan = true;
             }
         } else {
             // x slabs: cells overlapping |x - cx| < r: x_cell is monotone, one extra cell each side absorbs the
             // rounding of cx -+ r (cell width >> 1 ulp of x)
-            const int c_lo = max(0, x_cell(cx - rabs, hdr.xmin, hdr.inv_w) - 1);
-            const int c_hi = min(BQS_CELLS - 1, x_cell(cx + rabs, hdr.xmin, hdr.inv_w) + 1);
-            const int k0 = start[c_lo], kend = start[c_hi + 1];
+            const int c_lo = max(0, x_cell(cx - rabs, bv.hdr.xmin, bv.hdr.inv_w) - 1);
+            const int c_hi = min(BQS_CELLS - 1, x_cell(cx + rabs, bv.hdr.xmin, bv.hdr.inv_w) + 1);
+            const int k0 = bv.start[c_lo], kend = bv.start[c_hi + 1];
             if (kend - k0 <= BQS_MAX_SLAB) {
                 const int q = (kend - k0 + 3) >> 2;               // this wave's quarter of the slab
                 const int k = min(kend, k0 + w * q);
-                scan(k, min(kend, k + q));
+                bq_walk<BQS_UNROLL>(bv.sorted, k, min(kend, k + q), cx, cy, cz, rabs, radius2, row, cnt, nsample);
             } else {
                 full_scan = true;
             }
         }
-        if (full_scan && w == 0) {
-            // pathological density: ordered full scan with early exit (the reference's own loop)
-            for (int q = 0; q < n && cnt < nsample; ++q) {
-                const float d2 = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]);
-                if (d2 < radius2) { row[cnt] = (uint16_t)q; ++cnt; }
-            }
-        }
+        if (full_scan && w == 0) bq_ordered_scan(xyz, n, cx, cy, cz, radius2, row, cnt, nsample);   // pathological density
     }
     cnt_s[w * 64 + lane] = cnt;
     __syncthreads();
@@ -671,8 +748,7 @@ __global__ __launch_bounds__(256) void ball_query_sorted_kernel(int n, int m, in
             dst[total++] = (uint16_t)mn;
             i0 += (v0 == mn); i1 += (v1 == mn); i2 += (v2 == mn); i3 += (v3 == mn);
         }
-        const uint16_t first = total > 0 ? dst[0] : (uint16_t)0;
-        for (int s = total; s < nsample; ++s) dst[s] = first;
+        bq_pad_row(dst, total, nsample, 0, 1, nullptr, 0);
     }
     __syncthreads();
     if (w == 0) {
@@ -692,9 +768,7 @@ __global__ __launch_bounds__(256) void ball_query_sorted_kernel(int n, int m, in
 // ---- fine-grid flavour: 64 centres per workgroup, wave 0 searches (one lane per centre: the grid leaves ~5-30 candidates,
 // so the four-wave split and its merge are not worth their 33 KB of partial rows), then all four waves emit.  10 KB of LDS
 // per workgroup instead of 44 KB: 8 workgroups = 32 waves per CU instead of 12 -- the emit is latency-bound on its gathers,
-// and resident waves are what keeps loads in flight.  1-D grid, XCD-aware: workgroup g runs on XCD g % 8 (observed dispatch
-// order), so scene = (g / 8 / tiles) * 8 + g % 8 puts all tiles of a scene on ONE XCD -- its points and features are pulled
-// into one L2 instead of eight.
+// and resident waves are what keeps loads in flight.  1-D grid, XCD-aware (bq_tile_of).
 // Anatomy at the c2 shape (scripts/ablate_bq.sh, 512 scenes): search alone 0.16 ms, emit alone 0.61 ms (4.4 TB/s of stores), together
 // 0.78 ms.  A variant in which a workgroup takes 4 tiles and wave 0 searches tile t + 1 while waves 1-3 emit tile t was built and
 // measured: 0.90 ms -- the emit is bound by the issue capacity of its waves, not by load latency, so three emitting waves
@@ -709,26 +783,14 @@ __global__ __launch_bounds__(256) void ball_query_grid_kernel(int nb, int n, int
     int *cnt_s = reinterpret_cast<int *>(cen + 64);                    // 64
     uint16_t *rows = reinterpret_cast<uint16_t *>(cnt_s + 64);         // 64 * rstride
     const int rstride = nsample + 1;
-    const int tiles = (m + 63) / 64;
     int b, tile;
-    if ((nb & 7) == 0) {
-        const int g = blockIdx.x, j = g >> 3;
-        b = (j / tiles) * 8 + (g & 7);
-        tile = j - (j / tiles) * tiles;
-    } else {
-        b = blockIdx.x / tiles;
-        tile = blockIdx.x - b * tiles;
-    }
+    bq_tile_of(nb, (m + 63) / 64, b, tile);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int m0 = tile * 64;
     const int mi = m0 + lane;
     const bool active = mi < m;
     xyz += (size_t)b * n * 3;
-    const char *base = ws + (size_t)b * bin_scene_stride(n);
-    const float4 *sorted = reinterpret_cast<const float4 *>(base);
-    const BinHeader hdr = *reinterpret_cast<const BinHeader *>(base + (size_t)n * 16);
-    const uint16_t *start16 = reinterpret_cast<const uint16_t *>(base + (size_t)n * 16 + sizeof(BinHeader));
-    const int *params = reinterpret_cast<const int *>(base + (size_t)n * 16 + sizeof(BinHeader) + GRID16_PARAMS);
+    const BinView bv(ws, b, n);
     new_xyz += (size_t)b * m * 3;
     if (w == 0) {
         float cx = 0.f, cy = 0.f, cz = 0.f;
@@ -738,66 +800,25 @@ __global__ __launch_bounds__(256) void ball_query_grid_kernel(int nb, int n, int
         const float rabs = fabsf(radius);
         uint16_t *row = rows + (size_t)lane * rstride;
         int cnt = 0;
-        auto insert = [&](const int id) {  // keep the nsample smallest indices, ascending
-            if (cnt == nsample) {
-                if (id >= (int)row[nsample - 1]) return;
-                --cnt;
-            }
-            int pos = cnt;
-            while (pos > 0 && (int)row[pos - 1] > id) { row[pos] = row[pos - 1]; --pos; }
-            row[pos] = (uint16_t)id;
-            ++cnt;
-        };
 #ifdef WS3D_BQG_NO_SEARCH   // ablation (scripts/ablate_bq.sh): every centre "finds" 40 neighbours
         if (active) { for (int q = 0; q < 40 && q < nsample; ++q) row[q] = (uint16_t)((mi * 7 + q * 13) % n); cnt = min(40, nsample); }
         if (false) {
 #else
-        if (active && cx == cx && hdr.pad >= 0) {
-            // not a fine-grid buffer (see ball_query_grid_coop_kernel): the reference's ordered scan
-            for (int q = 0; q < n && cnt < nsample; ++q) {
-                const float d2 = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]);
-                if (d2 < radius2) { row[cnt] = (uint16_t)q; ++cnt; }
-            }
+        if (active && cx == cx && !bv.is_grid()) {
+            bq_ordered_scan(xyz, n, cx, cy, cz, radius2, row, cnt, nsample);      // not a fine-grid buffer (see bqc_search_tile)
         } else if (active && cx == cx) {
 #endif
-            // see ball_query_sorted_kernel for the bounds argument (hits lie within r (1 + 2^-23) of the centre on each axis)
-            const int gx = -hdr.pad, gz = params[2];
-            const float zmin = __int_as_float(params[0]), inv_wz = __int_as_float(params[1]);
-            const float sx = (fabsf(cx) + rabs) * 6e-7f, sz = (fabsf(cz) + rabs) * 6e-7f;
-            const int ix0 = grid_coord((cx - rabs) - sx, hdr.xmin, hdr.inv_w, gx), ix1 = grid_coord((cx + rabs) + sx, hdr.xmin, hdr.inv_w, gx);
-            const int iz0 = grid_coord((cz - rabs) - sz, zmin, inv_wz, gz), iz1 = grid_coord((cz + rabs) + sz, zmin, inv_wz, gz);
-            int total = 0;
-            for (int iz = iz0; iz <= iz1 && total <= BQS_MAX_SLAB; ++iz)
-                total += (int)start16[iz * gx + ix1 + 1] - (int)start16[iz * gx + ix0];
-            if (total <= BQS_MAX_SLAB) {
-                for (int iz = iz0; iz <= iz1; ++iz) {
-                    int k = (int)start16[iz * gx + ix0];
-                    const int ke = (int)start16[iz * gx + ix1 + 1];
-                    for (; k < ke; k += 4) {
-                        float4 p[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) p[u] = sorted[min(k + u, ke - 1)];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const float dx = cx - p[u].x;
-                            if (k + u < ke && fabsf(dx) < rabs) {
-                                const float d2 = sqdist3(dx, cy - p[u].y, cz - p[u].z);
-                                if (d2 < radius2) insert(__float_as_int(p[u].w));
-                            }
-                        }
-                    }
-                }
+            const BqGrid g = bv.grid();
+            const BqWindow win = bq_window(g, cx, cz, rabs);
+            if (bq_window_walkable(bv.start16, g.gx, win)) {
+                for (int iz = win.iz0; iz <= win.iz1; ++iz)
+                    bq_walk<4>(bv.sorted, (int)bv.start16[iz * g.gx + win.ix0], (int)bv.start16[iz * g.gx + win.ix1 + 1], cx, cy, cz, rabs, radius2,
+                               row, cnt, nsample);
             } else {
-                // pathological density: ordered full scan with early exit (the reference's own loop)
-                for (int q = 0; q < n && cnt < nsample; ++q) {
-                    const float d2 = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]);
-                    if (d2 < radius2) { row[cnt] = (uint16_t)q; ++cnt; }
-                }
+                bq_ordered_scan(xyz, n, cx, cy, cz, radius2, row, cnt, nsample);  // pathological density
             }
         }
-        const uint16_t first = cnt > 0 ? row[0] : (uint16_t)0;
-        for (int s2 = cnt; s2 < nsample; ++s2) row[s2] = first;
-        cnt_s[lane] = active ? cnt : 0;
+        bq_pad_row(row, cnt, nsample, 0, 1, &cnt_s[lane], active ? cnt : 0);
     }
     __syncthreads();
 #ifdef WS3D_BQG_NO_EMIT      // ablation: one word per workgroup keeps the search alive
@@ -848,11 +869,11 @@ constexpr int BQC_MAX_CAND = 8192;    // candidates tested per centre before the
 // blockIdx.y == 1 (ws3d_ball_query_pairs2, round 5): the SECOND scale of a set-abstraction level -- same points, centres and binned copy,
 // its own radius / nsample / outputs -- so that both searches of a level are ONE launch (a launch costs the 20-deep pipeline ~2.3 us).
 // The search of ONE tile of 64 centres by the NW waves of a workgroup (steps 1-4 of the comment above): fills rows[c][0 .. nsample) with the
-// padded lists, cnt_s[c] with the hit counts (0 for a centre beyond m) and cen[c] with the centres.  `base` = the scene's binned copy,
+// padded lists, cnt_s[c] with the hit counts (0 for a centre beyond m) and cen[c] with the centres.  bv = the scene's binned copy,
 // xyz / new_xyz = the scene's points / centres.  (A function of its own since round 6: a persistent search / emit pipeline was built on it and not kept, profiles/r06_bq_emit_anatomy.txt.)
 template <int NW>
 __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, const int m0, const int n, const int m, const float radius, const int nsample,
-                                                const float *__restrict__ xyz, const char *__restrict__ base, const float *__restrict__ new_xyz,
+                                                const float *__restrict__ xyz, const BinView &bv, const float *__restrict__ new_xyz,
                                                 float4 *cen, int *cnt_s, uint16_t *rows, const int rstride, uint16_t *hits_all, uint16_t *stage_all) {
     constexpr int CPW = 64 / NW;
     // grid rows fetched per centre and batch.  A wave of <= 8 centres has the lanes for EIGHT, and the r >= 0.5 m searches of the network span
@@ -878,10 +899,8 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
     }
     return;
 #endif
-    const float4 *sorted = reinterpret_cast<const float4 *>(base);
-    const BinHeader hdr = *reinterpret_cast<const BinHeader *>(base + (size_t)n * 16);
-    const uint16_t *start16 = reinterpret_cast<const uint16_t *>(base + (size_t)n * 16 + sizeof(BinHeader));
-    const int *params = reinterpret_cast<const int *>(base + (size_t)n * 16 + sizeof(BinHeader) + GRID16_PARAMS);
+    const float4 *sorted = bv.sorted;
+    const uint16_t *start16 = bv.start16;
     uint16_t *hits = hits_all + w * BQC_HCAP;
     uint16_t *stage = stage_all + w * (CPW * 64);
     const float radius2 = radius * radius;
@@ -889,9 +908,10 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
     // the host picks this kernel from what the sort entry points noted per buffer ADDRESS; a buffer of another flavour that
     // landed on a noted address (a copy, a recycled allocation) is recognised by its header and served by the ordered scan:
     // slow, never wrong
-    const bool not_grid = hdr.pad >= 0;
-    const int gx = not_grid ? 1 : -hdr.pad, gz = not_grid ? 1 : params[2];
-    const float zmin = __int_as_float(params[0]), inv_wz = __int_as_float(params[1]);
+    const bool not_grid = !bv.is_grid();
+    BqGrid g = bv.grid();
+    if (not_grid) g.gx = g.gz = 1;
+    const int gx = g.gx;
     const int id_bits = 32 - __builtin_clz(max(n - 1, 1));            // ids < n
 
     // ---- 1. this lane's (centre, row) of the wave's CPW centres x first R grid rows (lanes R CPW .. 63 idle)
@@ -902,12 +922,11 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
     if (q_l == 0 && ci_l < CPW) cen[CPW * w + ci_l] = make_float4(lcx, lcy, lcz, 0.f);
     int l_ix0 = 0, l_ix1 = 0, l_iz0 = 0, l_nrows = 0, l_k0 = 0, l_ke = 0;
     if (mi_l < m && lcx == lcx) {
-        // see ball_query_sorted_kernel for the bounds argument (hits lie within r (1 + 2^-23) of the centre on each axis)
-        const float sx = (fabsf(lcx) + rabs) * 6e-7f, sz = (fabsf(lcz) + rabs) * 6e-7f;
-        l_ix0 = grid_coord((lcx - rabs) - sx, hdr.xmin, hdr.inv_w, gx);
-        l_ix1 = grid_coord((lcx + rabs) + sx, hdr.xmin, hdr.inv_w, gx);
-        l_iz0 = grid_coord((lcz - rabs) - sz, zmin, inv_wz, gz);
-        l_nrows = grid_coord((lcz + rabs) + sz, zmin, inv_wz, gz) - l_iz0 + 1;
+        const BqWindow win = bq_window(g, lcx, lcz, rabs);
+        l_ix0 = win.ix0;
+        l_ix1 = win.ix1;
+        l_iz0 = win.iz0;
+        l_nrows = win.iz1 - win.iz0 + 1;
         if (not_grid) {
             l_nrows = 1;
         } else if (q_l < l_nrows) {
@@ -991,9 +1010,7 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
             __builtin_amdgcn_wave_barrier();
             if (simple_l) {
                 const int cnt = min(Hs, nsample);
-                const uint16_t first = cnt > 0 ? row[0] : (uint16_t)0;
-                for (int s2 = cnt + q_l; s2 < nsample; s2 += 4) row[s2] = first;
-                if (q_l == 0) cnt_s[c] = (m0 + c < m) ? cnt : 0;
+                bq_pad_row(row, cnt, nsample, q_l, 4, &cnt_s[c], (m0 + c < m) ? cnt : 0);
             }
         }
     }
@@ -1059,17 +1076,7 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
                     if (H > BQC_HCAP) ordered = true;
                 }
                 if (ordered) {
-                    // pathological density: the reference's ordered scan with early exit, 64 points per step
-                    for (int q0 = 0; q0 < n && cnt < nsample; q0 += 64) {
-                        const int q = q0 + lane;
-                        bool hit = false;
-                        if (q < n) hit = sqdist3(cx - xyz[q * 3 + 0], cy - xyz[q * 3 + 1], cz - xyz[q * 3 + 2]) < radius2;
-                        const uint64_t mask = __ballot(hit);
-                        const int pos = cnt + mbcnt(mask);
-                        if (hit && pos < nsample) row[pos] = (uint16_t)q;
-                        cnt += __popcll(mask);
-                    }
-                    cnt = min(cnt, nsample);
+                    cnt = bq_ordered_scan_wave(lane, xyz, n, cx, cy, cz, radius2, row, nsample);     // pathological density
                 } else if (H > nsample) {
                     // ---- 3. threshold: T = the nsample-th smallest index among the hits
                     int T = 0;
@@ -1115,12 +1122,9 @@ __device__ __forceinline__ void bqc_search_tile(const int lane, const int w, con
                 }
             }
         }
-        // pad with the first (smallest) entry; a centre without a hit: zeros (only the fused emit reads them)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
-        const uint16_t first = cnt > 0 ? row[0] : (uint16_t)0;
-        for (int s2 = cnt + lane; s2 < nsample; s2 += 64) row[s2] = first;
-        if (lane == 0) cnt_s[c] = (m0 + c < m) ? cnt : 0;
+        bq_pad_row(row, cnt, nsample, lane, 64, &cnt_s[c], (m0 + c < m) ? cnt : 0);
     }
 }
 
@@ -1146,22 +1150,13 @@ __global__ __launch_bounds__(64 * NW, (FUSED && NW == 4) ? BQC_FUSED_WPE : 1) vo
     const int rstride = nsample + 1;
     uint16_t *hits_all = rows + ((64 * rstride + 7) & ~7);            // NW waves x BQC_HCAP
     uint16_t *stage_all = hits_all + NW * BQC_HCAP;                    // NW waves x CPW centres x 64: the hits of each centre's first 64 candidates
-    const int tiles = (m + 63) / 64;
     int b, tile;
-    if ((nb & 7) == 0) {
-        const int g = blockIdx.x, j = g >> 3;
-        b = (j / tiles) * 8 + (g & 7);
-        tile = j - (j / tiles) * tiles;
-    } else {
-        b = blockIdx.x / tiles;
-        tile = blockIdx.x - b * tiles;
-    }
+    bq_tile_of(nb, (m + 63) / 64, b, tile);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     const int m0 = tile * 64;
     xyz += (size_t)b * n * 3;
-    const char *base = ws + (size_t)b * bin_scene_stride(n);
     new_xyz += (size_t)b * m * 3;
-    bqc_search_tile<NW>(lane, w, m0, n, m, radius, nsample, xyz, base, new_xyz, cen, cnt_s, rows, rstride, hits_all, stage_all);
+    bqc_search_tile<NW>(lane, w, m0, n, m, radius, nsample, xyz, BinView(ws, b, n), new_xyz, cen, cnt_s, rows, rstride, hits_all, stage_all);
     __syncthreads();
     if (!FUSED && rowc) {
         // ---- the compact (centre, source) pairs of these 64 lists (gemm_pool.hip pair_compact_kernel, here without a launch of
@@ -1201,9 +1196,86 @@ __global__ __launch_bounds__(64 * NW, (FUSED && NW == 4) ? BQC_FUSED_WPE : 1) vo
 }
 
 
-static size_t bq_smem(int nsample, size_t idx_bytes) {
-    return sizeof(float4) * (BQ_NW * BQ_TILE + 64) + sizeof(int) * BQ_NW * 64 +
-           idx_bytes * (size_t)BQ_NW * 64 * (nsample + 1);
+// What a search call launches.  family: BQ_BRUTE ball_query_kernel<uint16_t | int32_t, FUSED> (idx_bytes 2 | 4), BQ_SLAB
+// ball_query_sorted_kernel<FUSED>, BQ_LANE ball_query_grid_kernel<FUSED>, BQ_COOP ball_query_grid_coop_kernel<FUSED, nw>; nw waves per
+// workgroup, gz workgroups per tile of 64 centres (the fused emit's channel / row split), lds dynamic bytes; grid.x == 0: nothing to launch.
+enum { BQ_BRUTE = 0, BQ_SLAB = 1, BQ_LANE = 2, BQ_COOP = 3 };
+struct BqPlan { int family, idx_bytes, nw, gz; size_t lds; dim3 grid; };
+
+// The one place that decides.  flavour: what the sort entry points noted for the binned copy's address (1 fine grid, 0 anything else;
+// -1: no binned copy); pairs: the compact (centre, source) pairs are wanted; scales 2: both scales of a level in one launch (nsample =
+// the longer list; pairs implied); wide_nw: ws3d_tune key 5 (honoured by the two-scale launch only).  No HIP call.
+static int bq_plan(const char *what, int b, int n, int m, int c, int nsample, bool fused, bool nlc, int flavour, bool pairs, int scales,
+                   int wide_nw, BqPlan &p) {
+    p = BqPlan{BQ_BRUTE, 2, BQ_NW, 1, 0, dim3(0, 1, 1)};
+    if (b < 0 || n <= 0 || m < 0 || nsample <= 0 || c < 0) {
+        set_error("%s: invalid argument (b=%d n=%d m=%d nsample=%d c=%d)", what, b, n, m, nsample, c);
+        return WS3D_E_INVALID;
+    }
+    if (b == 0 || m == 0) return WS3D_OK;
+    const unsigned mt = (unsigned)((m + 63) / 64);
+    const long tiles = (long)b * mt;
+    // fused only: gz workgroups share a tile's search and split its emit -- channels-first by channels (at least 8 each), channels-last
+    // by (centre, sample) rows (at least 64 each) -- until 1024 workgroups fill the 256 CUs
+    if (fused && c >= 16) {
+        const long units = nlc ? 64L * nsample : c, least = nlc ? 64 : 8;
+        while (p.gz < 64 && tiles * p.gz < 1024 && units / (p.gz * 2) >= least) p.gz *= 2;
+    }
+    const bool binned = flavour >= 0 && n <= SORT_MAX_N && b <= 65535;
+    if (binned && flavour == 1) {
+        // one wave per centre; 16 waves x 4 centres per tile when the tiles alone do not fill the chip, else 4 x 16.
+        // ws3d_tune key 5 (round 6): 8 waves x 8 centres per tile instead of 16 x 4 in the two-scale launches that do not fill the chip -- a
+        // longer launch (level 2, r = 1.0: 26 -> 36 us alone) that holds half the waves: about +1 % on the 20-deep step
+        // (profiles/r06_bq_emit_anatomy.txt, section 10).  Stage1Pipeline sets it while it captures at depth >= 4; a lone caller keeps 16.
+        const bool wide = tiles * p.gz * scales < BQC_WIDE_BELOW;
+        const int nw = wide ? (scales == 2 && wide_nw == 8 ? 8 : 16) : BQC_LARGE_NW;
+        size_t lds = sizeof(float4) * 64 + sizeof(int) * 64 + sizeof(uint16_t) * (size_t)(((64 * (nsample + 1) + 7) & ~7) + nw * BQC_HCAP + 64 * 64);
+#ifdef WS3D_BQC_EXTRA_LDS     // occupancy probe (scripts/r06/bq_variants2.sh): unused LDS bytes per workgroup
+        lds += WS3D_BQC_EXTRA_LDS;
+#endif
+        if (nsample <= 64 && lds <= 64 * 1024 && (scales == 1 || tiles <= 0x7fffffffL)) {      // longer lists: one lane per centre (below)
+            p = BqPlan{BQ_COOP, 2, nw, p.gz, lds, dim3((unsigned)tiles, scales, p.gz)};
+            return WS3D_OK;
+        }
+        lds = sizeof(float4) * 64 + sizeof(int) * 64 + sizeof(uint16_t) * (size_t)64 * (nsample + 1);
+        if (!pairs && lds <= 64 * 1024) {
+            p = BqPlan{BQ_LANE, 2, 4, p.gz, lds, dim3((unsigned)tiles, 1, p.gz)};
+            return WS3D_OK;
+        }
+    }
+    if (pairs) {
+        set_error("%s: the pairs come out of the one-wave-per-centre fine-grid kernel only (sort_points_grid buffer, n <= %d, nsample <= 64; n=%d nsample=%d)%s",
+                  what, SORT_MAX_N, n, nsample, scales == 2 ? ": use ws3d_ball_query_pairs per scale" : "");
+        return WS3D_E_UNSUPPORTED;
+    }
+    if (binned) {
+        const size_t lds = sizeof(float4) * 64 + sizeof(int) * 256 + sizeof(uint16_t) * (size_t)5 * 64 * (nsample + 1);
+        if (lds <= 150 * 1024) {
+            p = BqPlan{BQ_SLAB, 2, 4, p.gz, lds, dim3(mt, b, p.gz)};
+            return WS3D_OK;
+        }
+    }
+    p.idx_bytes = n <= 65536 ? 2 : 4;   // neighbour lists held as uint16 in LDS where the indices fit
+    p.lds = sizeof(float4) * (BQ_NW * BQ_TILE + 64) + sizeof(int) * BQ_NW * 64 + (size_t)p.idx_bytes * BQ_NW * 64 * (nsample + 1);
+    if (p.lds > 160 * 1024 || b > 65535) {
+        set_error("%s: nsample=%d needs %zu B of LDS (> 160 KiB) or batch > 65535", what, nsample, p.lds);
+        return WS3D_E_UNSUPPORTED;
+    }
+    p.grid = dim3(mt, b, p.gz);
+    return WS3D_OK;
+}
+
+// every launch of the one-wave-per-centre kernel, single scale (second = {}) and two scales (grid.y == 2)
+template <bool FUSED>
+static int bqc_launch(const BqPlan &p, hipStream_t st, const char *what, int b, int n, int m, int c, float radius, int nsample, int use_xyz,
+                      const float *xyz, const void *sorted, const float *new_xyz, const float *features, int32_t *idx, float *out,
+                      int32_t *rowc, int32_t *rowsrc, int32_t *total, const BqScale2 &second) {
+    auto kernel = ball_query_grid_coop_kernel<FUSED, BQC_LARGE_NW>;
+    if (p.nw == 16) kernel = ball_query_grid_coop_kernel<FUSED, 16>;
+    if constexpr (!FUSED) { if (p.nw == 8) kernel = ball_query_grid_coop_kernel<false, 8>; }
+    hipLaunchKernelGGL(kernel, p.grid, dim3(64 * p.nw), p.lds, st, b, n, m, c, radius, nsample, use_xyz, xyz, reinterpret_cast<const char *>(sorted),
+                       new_xyz, features, idx, out, rowc, rowsrc, total, second);
+    return check_launch(what);
 }
 
 template <bool FUSED>
@@ -1211,80 +1283,35 @@ static int bq_launch(int b, int n, int m, int c, float radius, int nsample, int 
                      const float *xyz, const float *new_xyz, const float *features, int32_t *idx,
                      float *out, const void *sorted, hipStream_t st, const char *what, int nlc = 0,
                      int32_t *rowc = nullptr, int32_t *rowsrc = nullptr, int32_t *total = nullptr) {
-    if (b < 0 || n <= 0 || m < 0 || nsample <= 0 || c < 0 || !xyz || !new_xyz) {
-        set_error("%s: invalid argument (b=%d n=%d m=%d nsample=%d c=%d)", what, b, n, m, nsample, c);
-        return WS3D_E_INVALID;
-    }
+    if (!xyz || !new_xyz) { set_error("%s: invalid argument (xyz or new_xyz is NULL)", what); return WS3D_E_INVALID; }
     if (!FUSED && !idx) { set_error("%s: idx is NULL", what); return WS3D_E_INVALID; }
     if (FUSED && (!out || (c > 0 && !features) || (!use_xyz && c == 0))) {
         set_error("%s: out/features NULL or no channels", what);
         return WS3D_E_INVALID;
     }
-    if (b == 0 || m == 0) return WS3D_OK;
-    // channel split (fused only): enough workgroups to fill 256 CUs, at least 8 channels each
-    int gz = 1;
+    BqPlan p;
+    if (int rc = bq_plan(what, b, n, m, c, nsample, FUSED, nlc != 0, sorted ? (int)grid_flavour(sorted) : -1, rowc != nullptr, 1, 0, p)) return rc;
+    if (p.grid.x == 0) return WS3D_OK;
     use_xyz = FUSED ? ((use_xyz ? 1 : 0) | (nlc ? 2 : 0))   // bit 1 selects the channels-last epilogue (row-wise, no channel split)
                     : (use_xyz & 4);                        // index-only kernels: bit 2 = write zero rows for centres without a hit
-    if (FUSED && c >= 16 && !nlc) {
-        const long tiles = (long)b * ((m + 63) / 64);
-        while (gz < 64 && tiles * gz < 1024 && c / (gz * 2) >= 8) gz *= 2;
-    }
-    if (FUSED && nlc && c >= 16) {   // row slices: at least 64 rows per workgroup
-        const long tiles = (long)b * ((m + 63) / 64);
-        while (gz < 64 && tiles * gz < 1024 && (64L * nsample) / (gz * 2) >= 64) gz *= 2;
-    }
-    if (sorted && n <= SORT_MAX_N && b <= 65535 && grid_flavour(sorted)) {
-        // one wave per centre; 16 waves x 4 centres per tile when the tiles alone do not fill the chip, else 4 x 16
-        const bool wide = (long)b * ((m + 63) / 64) * gz < BQC_WIDE_BELOW;
-        const int nw = wide ? 16 : BQC_LARGE_NW;
-        size_t smem_c = sizeof(float4) * 64 + sizeof(int) * 64 + sizeof(uint16_t) * (size_t)(((64 * (nsample + 1) + 7) & ~7) + nw * BQC_HCAP + 64 * 64);
-#ifdef WS3D_BQC_EXTRA_LDS     // occupancy probe (scripts/r06/bq_variants2.sh): unused LDS bytes per workgroup
-        smem_c += WS3D_BQC_EXTRA_LDS;
-#endif
-        if (nsample <= 64 && smem_c <= 64 * 1024) {      // longer lists: one lane per centre (below)
-            if (wide)
-                hipLaunchKernelGGL((ball_query_grid_coop_kernel<FUSED, 16>), dim3((unsigned)(b * ((m + 63) / 64)), 1, gz), dim3(1024), smem_c, st, b, n, m, c,
-                                   radius, nsample, use_xyz, xyz, reinterpret_cast<const char *>(sorted), new_xyz, features, idx, out, rowc, rowsrc, total, BqScale2{});
-            else
-                hipLaunchKernelGGL((ball_query_grid_coop_kernel<FUSED, BQC_LARGE_NW>), dim3((unsigned)(b * ((m + 63) / 64)), 1, gz), dim3(64 * BQC_LARGE_NW), smem_c, st, b, n, m, c,
-                                   radius, nsample, use_xyz, xyz, reinterpret_cast<const char *>(sorted), new_xyz, features, idx, out, rowc, rowsrc, total, BqScale2{});
-            return check_launch(what);
+    const char *ws = reinterpret_cast<const char *>(sorted);
+    switch (p.family) {
+        case BQ_COOP:
+            return bqc_launch<FUSED>(p, st, what, b, n, m, c, radius, nsample, use_xyz, xyz, sorted, new_xyz, features, idx, out, rowc, rowsrc, total, BqScale2{});
+        case BQ_LANE:
+            hipLaunchKernelGGL((ball_query_grid_kernel<FUSED>), p.grid, dim3(256), p.lds, st, b, n, m, c, radius, nsample, use_xyz, xyz, ws, new_xyz,
+                               features, idx, out);
+            break;
+        case BQ_SLAB:
+            if (int rc = raise_lds_cap((const void *)ball_query_sorted_kernel<FUSED>, p.lds, what)) return rc;
+            hipLaunchKernelGGL((ball_query_sorted_kernel<FUSED>), p.grid, dim3(256), p.lds, st, n, m, c, radius, nsample, use_xyz, xyz, ws, new_xyz,
+                               features, idx, out);
+            break;
+        default: {
+            auto kernel = p.idx_bytes == 2 ? ball_query_kernel<uint16_t, FUSED> : ball_query_kernel<int32_t, FUSED>;
+            if (int rc = raise_lds_cap((const void *)kernel, p.lds, what)) return rc;
+            hipLaunchKernelGGL(kernel, p.grid, dim3(64 * BQ_NW), p.lds, st, n, m, c, radius, nsample, use_xyz, xyz, new_xyz, features, idx, out);
         }
-        if (rowc) { set_error("%s: nsample %d is not covered by the kernel that emits the pairs", what, nsample); return WS3D_E_UNSUPPORTED; }
-        const size_t smem_g = sizeof(float4) * 64 + sizeof(int) * 64 + sizeof(uint16_t) * (size_t)64 * (nsample + 1);
-        if (smem_g <= 64 * 1024) {
-            hipLaunchKernelGGL((ball_query_grid_kernel<FUSED>), dim3((unsigned)(b * ((m + 63) / 64)), 1, gz), dim3(256), smem_g, st, b, n, m, c,
-                               radius, nsample, use_xyz, xyz, reinterpret_cast<const char *>(sorted), new_xyz, features, idx, out);
-            return check_launch(what);
-        }
-    }
-    if (rowc) { set_error("%s: the pairs come out of the fine-grid kernel only (sort_points_grid buffer, n <= %d)", what, SORT_MAX_N); return WS3D_E_UNSUPPORTED; }
-    if (sorted && n <= SORT_MAX_N && b <= 65535) {
-        const size_t smem_s = sizeof(float4) * 64 + sizeof(int) * 256 +
-                              sizeof(uint16_t) * (size_t)5 * 64 * (nsample + 1);
-        if (smem_s <= 150 * 1024) {
-            if (int rc = raise_lds_cap((const void *)ball_query_sorted_kernel<FUSED>, smem_s, what)) return rc;
-            hipLaunchKernelGGL((ball_query_sorted_kernel<FUSED>), dim3((m + 63) / 64, b, gz), dim3(256), smem_s, st, n,
-                               m, c, radius, nsample, use_xyz, xyz, reinterpret_cast<const char *>(sorted),
-                               new_xyz, features, idx, out);
-            return check_launch(what);
-        }
-    }
-    const bool small_idx = n <= 65536;  // neighbour lists held as uint16 in LDS
-    const size_t smem = bq_smem(nsample, small_idx ? 2 : 4);
-    if (smem > 160 * 1024 || b > 65535) {
-        set_error("%s: nsample=%d needs %zu B of LDS (> 160 KiB) or batch > 65535", what, nsample, smem);
-        return WS3D_E_UNSUPPORTED;
-    }
-    dim3 grid((m + 63) / 64, b, gz);
-    if (small_idx) {
-        if (int rc = raise_lds_cap((const void *)ball_query_kernel<uint16_t, FUSED>, smem, what)) return rc;
-        hipLaunchKernelGGL((ball_query_kernel<uint16_t, FUSED>), grid, dim3(64 * BQ_NW), smem, st, n, m, c,
-                           radius, nsample, use_xyz, xyz, new_xyz, features, idx, out);
-    } else {
-        if (int rc = raise_lds_cap((const void *)ball_query_kernel<int32_t, FUSED>, smem, what)) return rc;
-        hipLaunchKernelGGL((ball_query_kernel<int32_t, FUSED>), grid, dim3(64 * BQ_NW), smem, st, n, m, c,
-                           radius, nsample, use_xyz, xyz, new_xyz, features, idx, out);
     }
     return check_launch(what);
 }
@@ -1500,40 +1527,30 @@ extern "C" int ws3d_ball_query_pairs2(int b, int n, int m, const float *new_xyz,
                                       float radius1, int nsample1, int32_t *idx1, int32_t *rowc1, int32_t *rowsrc1, int32_t *total1,
                                       ws3d_stream_t stream) {
     using namespace ws3d;
-    if (b < 0 || n <= 0 || m < 0 || nsample0 <= 0 || nsample1 <= 0 || !xyz || !new_xyz || !sorted_grid || !idx0 || !rowc0 || !rowsrc0 || !total0 ||
-        !idx1 || !rowc1 || !rowsrc1 || !total1) {
+    if (nsample0 <= 0 || nsample1 <= 0 || !xyz || !new_xyz || !sorted_grid || !idx0 || !rowc0 || !rowsrc0 || !total0 || !idx1 || !rowc1 || !rowsrc1 ||
+        !total1) {
         set_error("ws3d_ball_query_pairs2: invalid argument (b=%d n=%d m=%d nsample=%d/%d)", b, n, m, nsample0, nsample1);
         return WS3D_E_INVALID;
     }
-    if (b == 0 || m == 0) return WS3D_OK;
-    const int ns = nsample0 > nsample1 ? nsample0 : nsample1;
-    const long tiles = (long)b * ((m + 63) / 64);
-    const bool wide = tiles * 2 < BQC_WIDE_BELOW;
-    // ws3d_tune key 5 (round 6): 8 waves x 8 centres per tile instead of 16 x 4 in the launches that do not fill the chip -- a longer launch
-    // (level 2, r = 1.0: 26 -> 36 us alone) that holds half the waves: about +1 % on the 20-deep step (profiles/r06_bq_emit_anatomy.txt, section 10).
-    // Stage1Pipeline sets it while it captures at depth >= 4; a lone caller keeps 16.  Same lists, same pair sets.
-    constexpr int TUNE_BQ_WIDE_NW = 5;                         // (ws3d_tune key 5; the keys 0-4 are named in common.h)
-    static_assert(TUNE_BQ_WIDE_NW < TUNE_COUNT, "ws3d_tune key");
-    const bool wide8 = wide && g_tune[TUNE_BQ_WIDE_NW] == 8;
-    const int nw = wide ? (wide8 ? 8 : 16) : BQC_LARGE_NW;
-    const size_t smem_c = sizeof(float4) * 64 + sizeof(int) * 64 + sizeof(uint16_t) * (size_t)(((64 * (ns + 1) + 7) & ~7) + nw * BQC_HCAP + 64 * 64);
-    if (n > SORT_MAX_N || b > 65535 || tiles > 0x7fffffffL || ns > 64 || smem_c > 64 * 1024 || !grid_flavour(sorted_grid)) {
-        set_error("ws3d_ball_query_pairs2: not covered (n=%d nsample=%d/%d, or the binned copy is not a fine-grid one): use ws3d_ball_query_pairs per scale", n, nsample0, nsample1);
-        return WS3D_E_UNSUPPORTED;
-    }
-    const BqScale2 second{radius1, nsample1, idx1, rowc1, rowsrc1, total1};
-    hipStream_t st = as_stream(stream);
-    if (wide8)
-        hipLaunchKernelGGL((ball_query_grid_coop_kernel<false, 8>), dim3((unsigned)tiles, 2, 1), dim3(512), smem_c, st, b, n, m, 0, radius0, nsample0, 4, xyz,
-                           reinterpret_cast<const char *>(sorted_grid), new_xyz, (const float *)nullptr, idx0, (float *)nullptr, rowc0, rowsrc0, total0, second);
-    else if (wide)
-        hipLaunchKernelGGL((ball_query_grid_coop_kernel<false, 16>), dim3((unsigned)tiles, 2, 1), dim3(1024), smem_c, st, b, n, m, 0, radius0, nsample0, 4, xyz,
-                           reinterpret_cast<const char *>(sorted_grid), new_xyz, (const float *)nullptr, idx0, (float *)nullptr, rowc0, rowsrc0, total0, second);
-    else
-        hipLaunchKernelGGL((ball_query_grid_coop_kernel<false, BQC_LARGE_NW>), dim3((unsigned)tiles, 2, 1), dim3(64 * BQC_LARGE_NW), smem_c, st, b, n, m, 0, radius0,
-                           nsample0, 4, xyz, reinterpret_cast<const char *>(sorted_grid), new_xyz, (const float *)nullptr, idx0, (float *)nullptr, rowc0, rowsrc0,
-                           total0, second);
-    return check_launch("ws3d_ball_query_pairs2");
+    BqPlan p;
+    if (int rc = bq_plan("ws3d_ball_query_pairs2", b, n, m, 0, nsample0 > nsample1 ? nsample0 : nsample1, false, false, (int)grid_flavour(sorted_grid), true, 2,
+                         g_tune[TUNE_BQ_WIDE_NW], p))
+        return rc;
+    if (p.grid.x == 0) return WS3D_OK;
+    return bqc_launch<false>(p, as_stream(stream), "ws3d_ball_query_pairs2", b, n, m, 0, radius0, nsample0, 4, xyz, sorted_grid, new_xyz, nullptr, idx0, nullptr,
+                             rowc0, rowsrc0, total0, BqScale2{radius1, nsample1, idx1, rowc1, rowsrc1, total1});
+}
+
+extern "C" int ws3d_ball_query_plan(int b, int n, int m, int c, int nsample, int fused, int nlc, int flavour, int pairs, int scales, int wide_nw,
+                                    int32_t *plan) {
+    using namespace ws3d;
+    if (!plan || (scales != 1 && scales != 2)) { set_error("ws3d_ball_query_plan: plan is NULL or scales is not 1 / 2"); return WS3D_E_INVALID; }
+    BqPlan p;
+    const int rc = bq_plan("ws3d_ball_query_plan", b, n, m, c, nsample, fused != 0, nlc != 0, flavour, pairs != 0 || scales == 2, scales, wide_nw, p);
+    const bool none = rc != WS3D_OK || p.grid.x == 0;
+    const int32_t v[8] = {p.family, 8 * p.idx_bytes, fused != 0, p.nw, p.gz, (int32_t)p.lds, (int32_t)p.grid.x, (int32_t)p.grid.y};
+    for (int i = 0; i < 8; ++i) plan[i] = none ? 0 : v[i];
+    return rc;
 }
 
 extern "C" int ws3d_query_and_group(int b, int n, int m, int c, float radius, int nsample,
