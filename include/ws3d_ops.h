@@ -98,6 +98,17 @@ WS3D_API int ws3d_furthest_point_sampling_nested(int b, int n, int m, const floa
 WS3D_API int ws3d_furthest_point_sampling_nested_chain(int b, int n, int levels, const int *m, const float *xyz, int32_t *const *idx,
                                                        float *const *new_xyz, ws3d_stream_t stream);
 
+/* Furthest point sampling of `clouds` clouds of DIFFERENT sizes in one launch, one workgroup per cloud, points and running minimum
+ * on chip (no scratch).  xyz (total,3) packed; offsets (clouds+1) DEVICE int32 with offsets[0] = 0, cloud i = points offsets[i] ..
+ * offsets[i+1]; sizes_host (clouds) a HOST copy of the sizes offsets[i+1] - offsets[i] (validation and forwarding need them without
+ * a read-back); idx (clouds,m) out, indices LOCAL to each cloud.  idx[i] is bit-equal to ws3d_furthest_point_sampling(1, n_i, m, ..)
+ * on cloud i alone (the tie rule follows the cloud's own opt_n_threads(n_i)).  Clouds above ws3d_fps_ragged_limit() points (4096:
+ * 256 threads x 16 points) are forwarded to that entry, one launch each on the same stream (so n_i <= 65536).  clouds == 0 or
+ * m == 0: nothing is launched; any n_i < 1 or n_i < m: WS3D_E_INVALID before anything is launched.  No reference counterpart (the
+ * reference samples object by object from its dataset, kitti_rcnn_dataset.py:320-331).                                            */
+WS3D_API int ws3d_fps_ragged_limit(void);
+WS3D_API int ws3d_furthest_point_sampling_ragged(int clouds, const int32_t *offsets, const int32_t *sizes_host, int m, const float *xyz,
+                                                 int32_t *idx, ws3d_stream_t stream);
 
 /* gather_points_wrapper(b,c,n,npoints,points,idx,out)   sampling.cpp:11-20 ->
  * sampling_gpu.cu:8-37.  points (b,c,n), idx (b,npoints) -> out (b,c,npoints).     */

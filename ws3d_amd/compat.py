@@ -122,6 +122,29 @@ def furthest_point_sampling_nested(b, n, m, xyz, idx, new_xyz):
     return 1
 
 
+def fps_ragged_limit():
+    """the largest cloud ws3d_furthest_point_sampling_ragged keeps on chip (larger ones take the per-cloud kernel)"""
+    return int(_lib.load().ws3d_fps_ragged_limit())
+
+
+def furthest_point_sampling_ragged(xyz, offsets, sizes_host, m, idx):
+    """clouds of different sizes in one launch: xyz (T,3) packed, offsets (C+1,) int32 on the device, sizes_host a sequence of the C
+    sizes, idx (C,m) int32 out (indices local to each cloud).  ws3d extension."""
+    import ctypes as _ct
+    dev = _dev(xyz, offsets, idx)
+    _f32(xyz, "xyz"); _i32(offsets, "offsets"); _i32(idx, "idx")
+    C = len(sizes_host)
+    if offsets.numel() != C + 1 or tuple(idx.shape) != (C, m) or xyz.dim() != 2 or xyz.size(1) != 3:
+        raise Ws3dError(f"fps_ragged: xyz (T,3), offsets (C+1,), idx (C,m) expected, got {tuple(xyz.shape)} {tuple(offsets.shape)} {tuple(idx.shape)}")
+    if C and int(sum(sizes_host)) != xyz.size(0):
+        raise Ws3dError(f"fps_ragged: the sizes add up to {int(sum(sizes_host))} points, xyz holds {xyz.size(0)}")
+    sizes = (_ct.c_int32 * max(C, 1))(*[int(s) for s in sizes_host])
+    with _on(dev):
+        check(_lib.load().ws3d_furthest_point_sampling_ragged(C, _p(offsets), _ct.cast(sizes, _ct.c_void_p), m, _p(xyz), _p(idx), _stream()),
+              "fps_ragged")
+    return 1
+
+
 def furthest_point_sampling_nested_chain(xyz, npoints):
     """xyz (B, N, 3) in sampling order, npoints = the non-increasing sample counts of the levels below it -> [(idx, new_xyz), ...], one
     pair per level (level l samples level l-1's new_xyz): what len(npoints) calls of furthest_point_sampling_nested return, in four

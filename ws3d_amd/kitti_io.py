@@ -225,12 +225,16 @@ def sample_point_choice(pts_depth: np.ndarray, npoints: int, rng=np.random) -> n
 
 
 def rpn_input_from_scan(pts_lidar: np.ndarray, calib: Calibration, img_shape, npoints: int = 16384,
-                        random_select: bool = True, rng=np.random, area_scope=PC_AREA_SCOPE) -> np.ndarray:
+                        random_select: bool = True, rng=np.random, area_scope=PC_AREA_SCOPE, paste=None) -> np.ndarray:
     """``pts_input`` (npoints, 4) = [x, y, z (rect camera frame), intensity - 0.5] of one scan, as
-    ``get_rpn_sample`` builds it for inference (kitti_rcnn_dataset.py:399-452)"""
+    ``get_rpn_sample`` builds it for inference (kitti_rcnn_dataset.py:399-452).
+    paste: optional ``(pts_rect (N,3), intensity (N,)) -> (pts_rect, intensity)`` called where the reference pastes database objects
+    into a training scene (:404-414), before the validity filter -- so pasted points outside the image are clipped like scene points"""
     pts_lidar = pts_lidar[np.argsort(-pts_lidar[:, 2]), :]
     pts_rect = calib.lidar_to_rect(pts_lidar[:, 0:3])
     intensity = pts_lidar[:, 3]
+    if paste is not None:
+        pts_rect, intensity = paste(pts_rect, intensity)
     pts_img, depth = calib.rect_to_img(pts_rect)
     keep = valid_point_mask(pts_rect, pts_img, depth, img_shape, area_scope)
     pts_rect, intensity, depth = pts_rect[keep][:, 0:3], intensity[keep], depth[keep]

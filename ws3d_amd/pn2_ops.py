@@ -107,6 +107,33 @@ def furthest_point_sample_gather_nested_chain(xyz: torch.Tensor, npoints) -> lis
         return _C.furthest_point_sampling_nested_chain(xyz, npoints)
 
 
+def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoint: int) -> torch.Tensor:
+    """Furthest point sampling of C clouds of DIFFERENT sizes: xyz (T,3) packed, offsets (C+1,) int32 with offsets[0] = 0 and cloud
+    i = rows offsets[i] .. offsets[i+1] -> (C, npoint) int32 indices local to each cloud; row i equals
+    ``furthest_point_sample(cloud_i[None], npoint)[0]`` bit for bit (the tie rule follows each cloud's own size).
+    Device tensors: ONE launch, one workgroup per cloud (clouds above ``fps_ragged_limit()`` points are forwarded to the per-cloud
+    kernel).  CPU tensors: the numpy restatement ``fps_host`` -- the route of the loader processes, which never touch the device."""
+    npoint = int(npoint)
+    if xyz.dim() != 2 or xyz.size(1) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError(f"xyz (T,3) and offsets (C+1,) expected, got {tuple(xyz.shape)} {tuple(offsets.shape)}")
+    sizes = (offsets[1:] - offsets[:-1]).tolist()          # (a device tensor is read back once: the entry validates the sizes on the host)
+    if any(s < 1 or s < npoint for s in sizes) or npoint < 0:
+        raise ValueError(f"every cloud needs at least max(1, npoint={npoint}) points, got sizes {sorted(set(sizes))[:4]} ...")
+    if not xyz.is_cuda:
+        from . import _lib, fps_host
+        return torch.from_numpy(fps_host.furthest_point_sample_ragged(xyz.detach().float().numpy(), offsets.numpy(), npoint, _lib.DIST_MODE))
+    _dense(xyz=xyz, offsets=offsets)
+    idx = _new((len(sizes), npoint), torch.int32, xyz)
+    with torch.no_grad():
+        _C.furthest_point_sampling_ragged(xyz, offsets.to(torch.int32), sizes, npoint, idx)
+    return idx
+
+
+def fps_ragged_limit() -> int:
+    """the largest cloud the ragged kernel keeps on chip"""
+    return _C.fps_ragged_limit()
+
+
 def sampling_plan(xyz: torch.Tensor, npoints) -> list:
     """The backbone's chain of furthest-point samplings, ``[new_xyz_1 (B,npoints[0],3), new_xyz_2, ...]``
     with level k sampled from level k-1.  It depends on the coordinates only -- not on any weight --

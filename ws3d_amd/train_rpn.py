@@ -18,9 +18,17 @@ accepted for command-line compatibility: the weaklyRPN.yaml values live in ``sta
   * checkpoints ``ckpt/checkpoint_iter_%05d.pth`` = {'it', 'model_state', 'optimizer_state'}
     (train_utils.py:67-99) -- ``model_state`` interchanges with the reference (identical keys).
   * scene augmentation (rotation / scaling / flip, ``losses.scene_augmentation``) and the evaluation
-    pass of ``Trainer.eval_epoch_rpn`` (``evaluate``: loss, point precision, centre recall).
-Not reproduced: the reference's GT-sampling database (it needs the KITTI object crops) and
-tensorboard.  ``--mgpus`` maps to one process per GPU
+    pass of ``Trainer.eval_epoch_rpn`` (``evaluate``: loss, point precision, centre recall);
+  * the ground-truth paste augmentation (GT_AUG_ENABLED of weaklyRPN.yaml; kitti_rcnn_dataset.py:257-371, 404-414, 463-467) with
+    ``--gt_aug PATH [--gt_aug_prob P]``: up to 15 objects of the database ``python -m ws3d_amd.gt_database`` writes are pasted into
+    every training scene before it is filtered and sub-sampled, and their centres join the labels (``gt_paste``; host only, it runs
+    in the loader processes).  What is drawn per scene is the reference's; what is STORED is the 100-point subset of the "mimic
+    hard" objects, sampled once on the device when the database is built instead of once per draw -- the one place the scenes can
+    differ from the reference's in bits (``gt_paste`` docstring).  ``--synthetic N --gt_aug synthetic`` builds a database in memory
+    from ray-cast scenes, with easy_min_points lowered to 128 (about one ray-cast car in fifty exceeds the reference's 512 points).
+    Off by default: no flag, no paste.  The paste, the re-sampling and the labels of the added centres are host work per scene:
+    give --workers (measured at batch 8: 15 -> 51 ms/it without loader processes, 15 -> 17 ms/it with four; profiles/gt_paste.txt).
+Not reproduced: tensorboard.  ``--mgpus`` maps to one process per GPU
 (``torchrun``, DistributedDataParallel over RCCL) instead of ``nn.DataParallel``.
 """
 from __future__ import annotations
@@ -29,6 +37,7 @@ import argparse
 import logging
 import math
 import os
+import random
 import time
 from dataclasses import dataclass
 from typing import Iterator, Optional
@@ -38,7 +47,7 @@ import torch
 import torch.nn as nn
 from torch.nn.utils import clip_grad_norm_
 
-from . import kitti_io, loader, losses, pn2_ops, stage1
+from . import gt_paste, kitti_io, loader, losses, pn2_ops, stage1
 
 
 @dataclass(frozen=True)
@@ -167,29 +176,53 @@ def load_checkpoint(model: Optional[nn.Module] = None, optimizer=None, filename:
 
 
 # ----------------------------------------------------------------------------- data
-class SyntheticCenters:
+class _PasteStreams:
+    """the two random streams of the ground-truth paste: the dataset's numpy stream and a ``random.Random`` seeded from it on first
+    use IN THIS PROCESS (a forked loader process re-seeds the numpy stream, ``loader._init``, and so gets its own)"""
+    _pyrng = None
+
+    def _paste_pyrng(self, rng):
+        if self._pyrng is None or self._pyrng[0] != os.getpid():
+            self._pyrng = (os.getpid(), random.Random(int(rng.randint(0, 2 ** 31 - 1))))
+        return self._pyrng[1]
+
+
+class SyntheticCenters(_PasteStreams):
     """`count` seeded KITTI-shaped scenes with car-centre annotations (the weak labels of WS3D are
     BEV centre clicks): {'pts_input' (N,4), 'gt_centers' (K,3), 'rpn_cls_label', 'rpn_reg_label'}.
     labels=False: the two label entries are left out and not computed (they are made on the device, ``train(device_targets=True)``);
-    scenes, augmentation and the draws from `rng` are the same either way."""
+    scenes, augmentation and the draws from `rng` are the same either way.
+    gt_database (a ``gt_database.GtDatabase``): with probability gt_aug_prob the objects of one ``gt_paste`` draw are pasted into the
+    scene cloud, which is then sub-sampled back to npoints like a scan (``kitti_io.sample_point_choice`` on z), and their centres join
+    'gt_centers'.  None (the default): nothing is drawn, nothing changes."""
 
-    def __init__(self, count: int, npoints: int = 16384, config_id: int = 8, augment: bool = False, rng=np.random, labels: bool = True):
+    def __init__(self, count: int, npoints: int = 16384, config_id: int = 8, augment: bool = False, rng=np.random, labels: bool = True,
+                 gt_database=None, gt_aug_prob: float = 1.0):
         from . import synth
         self.synth, self.count, self.npoints, self.config_id = synth, count, npoints, config_id
         self.augment, self.rng, self.labels = augment, rng, labels
+        self.gt_database, self.gt_aug_prob = gt_database, gt_aug_prob
         self._scenes, self._items = {}, {}   # generated scans (and, without augmentation, their labels) are kept
 
     def __len__(self):
         return self.count
 
     def __getitem__(self, i: int) -> dict:
-        if not self.augment and i in self._items:
+        fixed = not self.augment and self.gt_database is None
+        if fixed and i in self._items:
             return self._items[i]
         if i not in self._scenes:
             seed = 1000 * self.config_id + i
             self._scenes[i] = (self.synth.lidar_cloud(self.npoints, seed),
                                self.synth.random_boxes3d(15, seed * 7919 + 13)[:, :3].astype(np.float32))
         pc, centres = self._scenes[i]
+        if self.gt_database is not None and self.rng.rand() < self.gt_aug_prob:
+            keep, obj_pts, obj_int, extra = gt_paste.plan_paste(pc[:, :3], centres, self.gt_database, self.rng, self._paste_pyrng(self.rng))
+            if keep is not None:        # the scene cloud carries intensity - 0.5, the database the raw value
+                pasted = np.concatenate((np.concatenate(obj_pts), np.concatenate(obj_int).reshape(-1, 1) - 0.5), axis=1)
+                pc = np.concatenate((pc[keep], pasted.astype(np.float32)), axis=0)
+                pc = pc[kitti_io.sample_point_choice(pc[:, 2], self.npoints, self.rng)]
+                centres = np.concatenate((centres, extra), axis=0)
         if self.augment:   # AUG_DATA (rotation / scaling / flip), like the reference's TRAIN loader
             xyz, centres, _ = losses.scene_augmentation(pc[:, :3], centres, self.rng)
             pc = np.concatenate((xyz.astype(np.float32), pc[:, 3:]), axis=1)
@@ -198,20 +231,25 @@ class SyntheticCenters:
         if self.labels:
             cls, reg = losses.gaussian_center_labels(pc[:, :3], centres)
             item.update({"rpn_cls_label": cls.astype(np.float32), "rpn_reg_label": reg})
-        if not self.augment:
+        if fixed:
             self._items[i] = item
         return item
 
 
-class KittiCenters:
+class KittiCenters(_PasteStreams):
     """KITTI directory: scans through ``kitti_io`` (no augmentation), centre annotations from
     label_2 (``noise_kind`` selects another label directory like the reference's --noise_kind), the
     first ``weakly_num`` scenes that contain a Car/Van.  labels=False: items carry 'pts_input' and 'gt_centers' only (see
-    SyntheticCenters)"""
+    SyntheticCenters).
+    gt_database (a ``gt_database.GtDatabase``; GT_AUG_ENABLED): like the reference's get_rpn_sample, ``rng.rand() < gt_aug_prob``
+    is drawn per scene and one ``gt_paste.paste_scene`` goes in between the projection to the camera frame and the validity filter;
+    the pasted centres are appended to the scene's own before the scene augmentation and the labels.  None: untouched."""
 
     def __init__(self, root: str, split: str = "train", npoints: int = 16384, noise_kind: Optional[str] = None,
-                 weakly_num: int = 500, rng=np.random, augment: bool = False, labels: bool = True):
+                 weakly_num: int = 500, rng=np.random, augment: bool = False, labels: bool = True, gt_database=None,
+                 gt_aug_prob: float = 1.0):
         self.augment, self.labels = augment, labels
+        self.gt_database, self.gt_aug_prob = gt_database, gt_aug_prob
         self.scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=rng)
         self.label_sub = noise_kind or "label_2"
         keep = []
@@ -237,9 +275,21 @@ class KittiCenters:
 
     def __getitem__(self, i: int) -> dict:
         sid = self.ids[i]
-        pts = kitti_io.rpn_input_from_scan(self.scenes.get_lidar(sid), self.scenes.get_calib(sid),
-                                           self.scenes.get_image_shape(sid), self.scenes.npoints, True, self.scenes.rng)
         centres = np.array([o.pos for o in self._objects(sid)], dtype=np.float32).reshape(-1, 3)
+        paste, extra = None, []
+        if self.gt_database is not None:
+            rng = self.scenes.rng
+
+            def paste(pts_rect, intensity):
+                if rng.rand() < self.gt_aug_prob:
+                    pts_rect, intensity, added = gt_paste.paste_scene(pts_rect, intensity, centres, self.gt_database, rng,
+                                                                      self._paste_pyrng(rng))
+                    extra.append(added)
+                return pts_rect, intensity
+        pts = kitti_io.rpn_input_from_scan(self.scenes.get_lidar(sid), self.scenes.get_calib(sid),
+                                           self.scenes.get_image_shape(sid), self.scenes.npoints, True, self.scenes.rng, paste=paste)
+        if extra:
+            centres = np.concatenate((centres, extra[0]), axis=0)
         if self.augment:
             xyz, centres, _ = losses.scene_augmentation(pts[:, :3], centres, self.scenes.rng)
             pts = np.concatenate((xyz, pts[:, 3:]), axis=1)
@@ -525,6 +575,25 @@ def _train_loop(net, model, optimizer, stream, it, total_iters, net_cfg, train_c
             "step_ms": step_ms}
 
 
+def synthetic_gt_database(log=None, scenes: int = 8):
+    """a paste database built in memory from `scenes` ray-cast scenes.  Only about one ray-cast car in fifty exceeds the reference's
+    512 points, too few to draw 10 easy objects from, so this route lowers easy_min_points to 128 (and says so)"""
+    from . import gt_database as gdb
+    records = gdb.build_gt_database(gdb.synthetic_scenes(scenes), easy_min_points=gdb.SYNTHETIC_EASY_MIN_POINTS)
+    db = gdb.GtDatabase(records)
+    if log:
+        log.info("synthetic gt database from %d ray-cast scenes: %d easy (more than %d points, NOT the reference's 512), %d hard",
+                 scenes, len(db.easy), gdb.SYNTHETIC_EASY_MIN_POINTS, len(db.hard))
+    return db
+
+
+def _load_gt_aug(path, last_sample_id):
+    if not path:
+        return None
+    from . import gt_database as gdb
+    return gdb.load_gt_database(path, last_sample_id)
+
+
 def main():
     ap = argparse.ArgumentParser(description="Stage-1 RPN trainer (flags of the reference's tools/train_rpn.py)")
     ap.add_argument("--cfg_file", type=str, default="cfgs/", help="accepted for compatibility; weaklyRPN values are built in")
@@ -544,6 +613,10 @@ def main():
     ap.add_argument("--synthetic", type=int, default=0, help="train on this many seeded synthetic scenes instead")
     ap.add_argument("--device_targets", action="store_true", default=False,
                     help="upload scenes and centres, make the labels on the device and take the loss from fused HIP (off: labels on the host)")
+    ap.add_argument("--gt_aug", type=str, default=None,
+                    help="ground-truth paste augmentation: the database written by `python -m ws3d_amd.gt_database`, or 'synthetic' "
+                         "(with --synthetic: built in memory from ray-cast scenes).  Off without the flag")
+    ap.add_argument("--gt_aug_prob", type=float, default=1.0, help="GT_AUG_APPLY_PROB: share of the scenes that get a paste")
     a = ap.parse_args()
     logging.basicConfig(level=logging.INFO, format="%(asctime)s  %(levelname)5s  %(message)s")
     out_dir = a.output_dir or os.path.join("output", "rpn", "weaklyRPN")
@@ -553,10 +626,14 @@ def main():
         from . import dist as wdist
         _, _, local = wdist.init()
     if a.synthetic:
-        ds = SyntheticCenters(a.synthetic, labels=not a.device_targets)
+        db = synthetic_gt_database(logging.getLogger("ws3d_amd.train_rpn")) if a.gt_aug == "synthetic" else _load_gt_aug(a.gt_aug, None)
+        ds = SyntheticCenters(a.synthetic, labels=not a.device_targets, gt_database=db, gt_aug_prob=a.gt_aug_prob)
     elif a.data_root:
         label_dir = a.noise_kind if os.path.isdir(os.path.join(a.data_root, "training", a.noise_kind)) else None
-        ds = KittiCenters(a.data_root, "train", noise_kind=label_dir, weakly_num=a.weakly_num, labels=not a.device_targets)
+        ds = KittiCenters(a.data_root, "train", noise_kind=label_dir, weakly_num=a.weakly_num, labels=not a.device_targets,
+                          gt_aug_prob=a.gt_aug_prob)
+        if a.gt_aug:                        # the reader's filter: objects of the scans up to the last training scene (:78)
+            ds.gt_database = _load_gt_aug(a.gt_aug, ds.ids[-1] if ds.ids else None)
     else:
         ap.error("give --data_root or --synthetic N")
     res = train(ds, a.total_iters, a.batch_size, out_dir, a.ckpt, a.pretrain_ckpt, a.ckpt_save_interval,
