@@ -840,6 +840,26 @@ WS3D_API int ws3d_rpn_loss(int rows, int bins, double loc_scope, double loc_bin_
                            float *vals, int32_t *counts, float *grad_cls, float *grad_reg, void *workspace, size_t workspace_bytes,
                            ws3d_stream_t stream);
 
+/* Raw KITTI scans -> pts_input on the device: the projection, frustum / range filter and npoints-row sample that
+ * kitti_io.rpn_input_from_scan does per scene on the host (get_rpn_sample, lib/datasets/kitti_rcnn_dataset.py:399-452), for a ragged
+ * batch in one call with no read-back.  ANOTHER random stream than the reference's (counter-based, keyed by (seed, scene_key)) and no
+ * sort by lidar z: DESIGN.md "Scan preparation on the device" states the contract, ws3d_amd/scan_prepare.py restates it bit for bit.
+ *   offsets (scenes + 1) int32: scene b holds the raw points offsets[b] .. offsets[b+1] of raw (total_points, 4) [x, y, z, refl]
+ *   (16-byte aligned); max_scan_points: the largest scan of the call; calib (scenes, 24): T (4 x 3) = V2C^T . R0^T, then P2 (3 x 4);
+ *   img_hw (scenes, 2) int32 = height, width; scope: HOST pointer to x0 x1 y0 y1 z0 z1 or NULL (no range filter); scene_key (scenes)
+ *   int64; key_bits 1..32 (32 in production; fewer bits force ties) ->
+ *   pts_input (scenes, npoints, 4) = [r_0, r_1, r_2, refl - 0.5f] (16-byte aligned), src_index (scenes, npoints) = the raw index of
+ *   each row, valid_count (scenes) = V, status (scenes): 0 ok; 1 no valid point; 2 more than npoints points beyond 40 m; 3 offsets
+ *   that do not describe a slice of raw.  A scene with a non-zero status gets zero rows and src_index -1 and leaves the others alone.
+ * WS3D_E_UNSUPPORTED: npoints above ws3d_scan_prepare_limit(), npoints * max_scan_points above 2^32 or more than 65535 scenes.
+ * workspace: ws3d_scan_prepare_workspace_bytes(scenes, total_points) bytes, 4-byte aligned.  Two launches on `stream`.            */
+WS3D_API int ws3d_scan_prepare_limit(void);
+WS3D_API size_t ws3d_scan_prepare_workspace_bytes(int scenes, long total_points);
+WS3D_API int ws3d_scan_prepare(int scenes, const int32_t *offsets, long total_points, int max_scan_points, const float *raw, const float *calib,
+                               const int32_t *img_hw, const float *scope, int npoints, uint64_t seed, const int64_t *scene_key, int key_bits,
+                               float *pts_input, int32_t *src_index, int32_t *valid_count, int32_t *status, void *workspace,
+                               size_t workspace_bytes, ws3d_stream_t stream);
+
 /* ------------------------------------------------- test hooks */
 
 /* What ws3d_roipool3d / _fill / _ws would launch for these sizes under this process's WS3D_ROI_* knobs, without launching it:

@@ -18,7 +18,7 @@ import os
 import numpy as np
 import torch
 
-from . import annotate, kitti_io, stage2
+from . import annotate, kitti_io, scan_prepare, stage2
 from .detect_kitti import load_stage2
 
 
@@ -40,17 +40,19 @@ def _pad(rows: list, width: int):
 
 
 def run(root: str, split: str, out_dir: str, batch: int = 4, rcnn_ckpt: str | None = None, click_labels: str | None = None, npoints: int = 16384,
-        seed: int = 666, device: str = "cuda:0", cfg: stage2.RCNNConfig = annotate.ANNOTATE_CFG, rcnn_batch: int = 800):
+        seed: int = 666, device: str = "cuda:0", cfg: stage2.RCNNConfig = annotate.ANNOTATE_CFG, rcnn_batch: int = 800,
+        device_ingest: str = "off"):
     """returns (the result files written, one per scene and possibly empty; recalled per ``annotate.RECALL_THRESHOLDS``; total ground truths)"""
     dev = torch.device(device)
     s2 = load_stage2(rcnn_ckpt, device, cfg)
     scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=np.random.RandomState(seed))     # eval_active.py seeds numpy with 666
+    dataset = scan_prepare.driver_dataset(scenes, device_ingest)
     os.makedirs(out_dir, exist_ok=True)
     written, recalled, total = [], [0] * len(annotate.RECALL_THRESHOLDS), 0
     for i0 in range(0, len(scenes), batch):
-        items = [scenes[i] for i in range(i0, min(i0 + batch, len(scenes)))]
+        items = [dataset[i] for i in range(i0, min(i0 + batch, len(scenes)))]
         ids = [int(item["sample_id"]) for item in items]
-        pts = torch.from_numpy(kitti_io.collate_scenes(items)["pts_input"]).to(dev)
+        pts = torch.as_tensor(scan_prepare.batch_points(items, device_ingest, npoints, seed, dev)).to(dev)
         clicks, num = _pad([car_boxes(os.path.join(scenes.imageset_dir, click_labels or "label_2", "%06d.txt" % sid))[:, :3] for sid in ids], 3)
         gt, gt_num = _pad([car_boxes(os.path.join(scenes.imageset_dir, "label_2", "%06d.txt" % sid)) for sid in ids], 7)
         boxes, scores, count, _ = annotate.annotate_batch(s2, pts, torch.from_numpy(clicks).to(dev), torch.from_numpy(num).to(dev), cfg, rcnn_batch)
@@ -80,10 +82,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--rcnn_batch", type=int, default=800, help="instance clouds per Stage-2 forward")
     ap.add_argument("--npoints", type=int, default=16384)
+    ap.add_argument("--device_ingest", default="off", choices=scan_prepare.ROUTES,
+                    help="off: the reference's host sampler (default); device: project, filter and sample the raw scans in one HIP call "
+                         "(ws3d_amd.scan_prepare, another random stream); host: the same rows computed on the host")
     ap.add_argument("--eval", action="store_true",
                     help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
     a = ap.parse_args()
-    files, recalled, total = run(a.root, a.split, a.out, a.batch, a.rcnn_ckpt, a.click_labels, a.npoints, rcnn_batch=a.rcnn_batch)
+    files, recalled, total = run(a.root, a.split, a.out, a.batch, a.rcnn_ckpt, a.click_labels, a.npoints, rcnn_batch=a.rcnn_batch, device_ingest=a.device_ingest)
     print(f"{len(files)} result files in {a.out}")
     print(recall_table(recalled, total), end="")
     if a.eval:

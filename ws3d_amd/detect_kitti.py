@@ -17,7 +17,7 @@ import os
 import numpy as np
 import torch
 
-from . import kitti_io, stage1, stage2
+from . import kitti_io, scan_prepare, stage1, stage2
 
 OUT_KEYS = ("rcnn_cls", "rcnn_iou", "rcnn_ref", "box_ce")
 
@@ -77,15 +77,16 @@ def detect_batch(s1, s2, pts: torch.Tensor, cfg: stage1.RPNConfig = stage1.DEFAU
 
 def run(root: str, split: str, out_dir: str, batch: int = 4, ckpt: str | None = None, rcnn_ckpt: str | None = None, npoints: int = 16384,
         seed: int = 666, device: str = "cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG,
-        rcnn_batch: int = 800) -> list:
+        rcnn_batch: int = 800, device_ingest: str = "off") -> list:
     """returns the list of result files written (one per scene, possibly empty)"""
     s1, s2 = load_models(ckpt, rcnn_ckpt, device, cfg, rcnn_cfg)
     scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=np.random.RandomState(seed))     # eval_auto.py:139 seeds numpy with 666
+    dataset = scan_prepare.driver_dataset(scenes, device_ingest)
     os.makedirs(out_dir, exist_ok=True)
     written = []
     for i0 in range(0, len(scenes), batch):
-        items = [scenes[i] for i in range(i0, min(i0 + batch, len(scenes)))]
-        pts = torch.from_numpy(kitti_io.collate_scenes(items)["pts_input"]).to(torch.device(device))
+        items = [dataset[i] for i in range(i0, min(i0 + batch, len(scenes)))]
+        pts = torch.as_tensor(scan_prepare.batch_points(items, device_ingest, npoints, seed, device)).to(torch.device(device))
         boxes, scores, count = (t.cpu().numpy() for t in detect_batch(s1, s2, pts, cfg, rcnn_cfg, rcnn_batch))
         for j, item in enumerate(items):
             sid, k = int(item["sample_id"]), int(count[j])
@@ -104,10 +105,13 @@ def main():
     ap.add_argument("--batch", type=int, default=4)
     ap.add_argument("--rcnn_batch", type=int, default=800, help="instance clouds per Stage-2 forward (the reference's Stage-2 batch)")
     ap.add_argument("--npoints", type=int, default=16384)
+    ap.add_argument("--device_ingest", default="off", choices=scan_prepare.ROUTES,
+                    help="off: the reference's host sampler (default); device: project, filter and sample the raw scans in one HIP call "
+                         "(ws3d_amd.scan_prepare, another random stream); host: the same rows computed on the host")
     ap.add_argument("--eval", action="store_true",
                     help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
     a = ap.parse_args()
-    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.rcnn_ckpt, a.npoints, rcnn_batch=a.rcnn_batch)
+    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.rcnn_ckpt, a.npoints, rcnn_batch=a.rcnn_batch, device_ingest=a.device_ingest)
     print(f"{len(files)} result files in {a.out}")
     if a.eval:
         from . import kitti_eval

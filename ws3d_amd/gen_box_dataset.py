@@ -22,7 +22,7 @@ import pickle
 import numpy as np
 import torch
 
-from . import kitti_io, stage1
+from . import kitti_io, scan_prepare, stage1
 
 FG_DIST, MATCH_DIST, BOX_SCALE, RADIUS = 0.7, 1.5, 1.2, 4.0
 
@@ -65,7 +65,7 @@ def label_instance(center: np.ndarray, cur_box_point: np.ndarray, gt_boxes3d: np
 
 def run(root: str, split: str, out_dir: str, batch: int = 8, ckpt: str | None = None, score_thresh: float = 0.1,
         with_features: bool = False, npoints: int = 16384, seed: int = 666, device: str = "cuda:0",
-        cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, hook=None) -> str:
+        cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, hook=None, device_ingest: str = "off") -> str:
     """writes ``out_dir/<split>_boxes.pkl`` and returns its path.  hook(sample_id, pts_input (N,4), scores (N,)): called once per
     scene with the host copies of what the clouds were cut from."""
     from . import instance_ops
@@ -79,10 +79,11 @@ def run(root: str, split: str, out_dir: str, batch: int = 8, ckpt: str | None = 
         from .seeded import seeded_state_dict
         model.load_state_dict(seeded_state_dict({k: tuple(v.shape) for k, v in model.state_dict().items()}, 0))
     scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=np.random.RandomState(seed))
+    dataset = scan_prepare.driver_dataset(scenes, device_ingest)
     database = []
     for i0 in range(0, len(scenes), batch):
-        items = [scenes[i] for i in range(i0, min(i0 + batch, len(scenes)))]
-        pts = torch.from_numpy(kitti_io.collate_scenes(items)["pts_input"]).to(dev)
+        items = [dataset[i] for i in range(i0, min(i0 + batch, len(scenes)))]
+        pts = torch.as_tensor(scan_prepare.batch_points(items, device_ingest, npoints, seed, dev)).to(dev)
         B, N = pts.shape[0], pts.shape[1]
         with torch.no_grad():
             out = model.rpn_forward({"pts_input": pts})
@@ -136,8 +137,11 @@ def main():
     ap.add_argument("--score_thresh", type=float, default=0.1)
     ap.add_argument("--with_features", action="store_true")
     ap.add_argument("--npoints", type=int, default=16384)
+    ap.add_argument("--device_ingest", default="off", choices=scan_prepare.ROUTES,
+                    help="off: the reference's host sampler (default); device: project, filter and sample the raw scans in one HIP call "
+                         "(ws3d_amd.scan_prepare, another random stream); host: the same rows computed on the host")
     a = ap.parse_args()
-    path = run(a.root, a.split, a.out, a.batch, a.ckpt, a.score_thresh, a.with_features, a.npoints)
+    path = run(a.root, a.split, a.out, a.batch, a.ckpt, a.score_thresh, a.with_features, a.npoints, device_ingest=a.device_ingest)
     with open(path, "rb") as f:
         print(f"{len(pickle.load(f))} instances in {path}")
 

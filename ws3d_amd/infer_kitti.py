@@ -18,13 +18,13 @@ import os
 import numpy as np
 import torch
 
-from . import kitti_io, loader, stage1
+from . import kitti_io, loader, scan_prepare, stage1
 from .pipeline import Stage1Pipeline, ensure_hw_queues
 
 
 def run(root: str, split: str, out_dir: str, batch: int = 8, ckpt: str | None = None, npoints: int = 16384,
         seed: int = 666, device: str = "cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, depth: int = 4,
-        workers: int = 0) -> list:
+        workers: int = 0, device_ingest: str = "off") -> list:
     """returns the list of result files written (one per scene, possibly empty)"""
     dev = torch.device(device)
     model = stage1.Stage1Net(mode="TEST", cfg=cfg).to(dev).eval()
@@ -41,11 +41,13 @@ def run(root: str, split: str, out_dir: str, batch: int = 8, ckpt: str | None = 
     starts = list(range(0, len(scenes), batch))
     loaded = {}
 
+    dataset = scan_prepare.driver_dataset(scenes, device_ingest)     # device_ingest: the loader processes only read files
+
     def batches():      # scans read + sampled in `workers` loader processes when asked for (ws3d_amd.loader)
         ids = [list(range(i0, min(i0 + batch, len(scenes)))) for i0 in starts]
-        for i0, items in zip(starts, loader.item_batches(scenes, ids, workers, ahead=depth + 1, seed=seed)):
+        for i0, items in zip(starts, loader.item_batches(dataset, ids, workers, ahead=depth + 1, seed=seed)):
             loaded[i0] = items
-            yield kitti_io.collate_scenes(items)["pts_input"]
+            yield scan_prepare.batch_points(items, device_ingest, npoints, seed, dev)
 
     # `depth` batches in flight (ws3d_amd.pipeline): the next scans are read and sampled on the host while the device works
     pipe = Stage1Pipeline(model, cfg, batch=batch, n_points=npoints, depth=depth, device=dev)
@@ -68,11 +70,14 @@ def main():
     ap.add_argument("--npoints", type=int, default=16384)
     ap.add_argument("--pipeline_depth", type=int, default=4, help="batches in flight on separate HIP streams")
     ap.add_argument("--workers", type=int, default=0, help="loader processes reading / sampling the next scans")
+    ap.add_argument("--device_ingest", default="off", choices=scan_prepare.ROUTES,
+                    help="off: the reference's host sampler (default); device: project, filter and sample the raw scans in one HIP call "
+                         "(ws3d_amd.scan_prepare, another random stream); host: the same rows computed on the host")
     ap.add_argument("--eval", action="store_true",
                     help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
     a = ap.parse_args()
     ensure_hw_queues()
-    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.npoints, depth=a.pipeline_depth, workers=a.workers)
+    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.npoints, depth=a.pipeline_depth, workers=a.workers, device_ingest=a.device_ingest)
     print(f"{len(files)} result files in {a.out}")
     if a.eval:
         from . import kitti_eval

@@ -336,6 +336,12 @@ class KittiScenes:
                                         self.get_image_shape(sample_id), self.npoints, self.random_select, self.rng)
         return {"sample_id": sample_id, "random_select": self.random_select, "pts_input": pts_input}
 
+    def raw_item(self, index: int) -> dict:
+        """the files of one scene and nothing sampled: what ``ws3d_amd.scan_prepare`` turns into ``pts_input``"""
+        sample_id = self.sample_id_list[index]
+        return {"sample_id": sample_id, "pts_lidar": self.get_lidar(sample_id), "calib": self.get_calib(sample_id),
+                "img_shape": self.get_image_shape(sample_id)}
+
 
 def collate_scenes(samples: Sequence[dict]) -> dict:
     """batch of equal-size scenes -> {'sample_id': (B,), 'pts_input': (B,N,4) float32}"""
