@@ -81,6 +81,18 @@ WS3D_API int ws3d_furthest_point_sampling(int b, int n, int m, const float *xyz,
 WS3D_API int ws3d_furthest_point_sampling_gather(int b, int n, int m, const float *xyz, float *temp,
                                         int32_t *idx, float *new_xyz, ws3d_stream_t stream);
 
+/* ws3d_furthest_point_sampling[_gather] with a caller-provided scratch buffer: for scenes of ws3d_fps_workspace_bytes(b, n) > 0
+ * bytes (16384 < n <= 65536; a pure host function, linear in b, a multiple of 16) the scene is counting-sorted once into Z-order
+ * buckets of 64 points inside `workspace` and every step updates only the buckets whose bounding box the new sample can reach
+ * (fps_pruned.hip: the skip is exact).  idx, temp and new_xyz (may be NULL) equal those of the plain entries bit for bit for ANY
+ * input and any initial temp (NULL: 1e10 assumed, nothing written back), ties included.  workspace NULL / too small / not 16-byte
+ * aligned, n outside that range, or WS3D_FPS_PRUNED=0 in the environment (read once): this IS ws3d_furthest_point_sampling_gather,
+ * return codes included.  Contents undefined on return; nothing is allocated or synchronised.  ws3d extension (ABI 6). */
+WS3D_API size_t ws3d_fps_workspace_bytes(int b, int n);
+WS3D_API int ws3d_furthest_point_sampling_ws(int b, int n, int m, const float *xyz, float *temp, int32_t *idx,
+                                             float *new_xyz /* may be NULL */, void *workspace, size_t workspace_bytes,
+                                             ws3d_stream_t stream);
+
 /* FPS + gather of a cloud that is ALREADY in sampling order -- level l+1 of a set-abstraction stack samples the centres
  * level l selected, in the order it selected them (pointnet2_msg.py:56-70) -- where greedy selection returns idx = 0..m-1
  * unless two points tie for a maximum.  Same results as ws3d_furthest_point_sampling_gather for ANY input: the nesting is

@@ -43,6 +43,8 @@ SIGNATURES = {
     "ws3d_furthest_point_sampling_nested_chain": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_fps_ragged_limit": (_i, []),
     "ws3d_furthest_point_sampling_ragged": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp]),
+    "ws3d_fps_workspace_bytes": (_sz, [_i, _i]),
+    "ws3d_furthest_point_sampling_ws": (_i, [_i, _i, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ws3d_gather_points": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ws3d_gather_points_grad": (_i, [_i, _i, _i, _i, _vp, _vp, _vp, _vp]),
     "ws3d_ball_query": (_i, [_i, _i, _i, _f, _i, _vp, _vp, _vp, _vp, _vp]),

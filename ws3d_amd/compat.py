@@ -96,9 +96,16 @@ def furthest_point_sampling_wrapper(b, n, m, points_tensor, temp_tensor, idx_ten
     """sampling.cpp:36-46"""
     dev = _dev(points_tensor, temp_tensor, idx_tensor)
     _f32(points_tensor, "xyz"); _i32(idx_tensor, "idx")
+    lib = _lib.load()
     with _on(dev):
-        check(_lib.load().ws3d_furthest_point_sampling(b, n, m, _p(points_tensor), _p(temp_tensor),
-                                                        _p(idx_tensor), _stream()), "furthest_point_sampling")
+        nbytes = lib.ws3d_fps_workspace_bytes(b, n)
+        if nbytes:          # 16384 < n <= 65536: the pruned kernels (fps_pruned.hip), out of a scratch buffer from the caching allocator
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(lib.ws3d_furthest_point_sampling_ws(b, n, m, _p(points_tensor), _p(temp_tensor), _p(idx_tensor), None, _p(ws), nbytes,
+                                                      _stream()), "furthest_point_sampling")
+        else:
+            check(lib.ws3d_furthest_point_sampling(b, n, m, _p(points_tensor), _p(temp_tensor),
+                                                   _p(idx_tensor), _stream()), "furthest_point_sampling")
     return 1
 
 
@@ -106,9 +113,15 @@ def furthest_point_sampling_gather(b, n, m, xyz, temp, idx, new_xyz):
     """fused a1+a2 (ws3d extension; no reference counterpart)"""
     dev = _dev(xyz, temp, idx, new_xyz)
     _f32(xyz, "xyz"); _i32(idx, "idx")
+    lib = _lib.load()
     with _on(dev):
-        check(_lib.load().ws3d_furthest_point_sampling_gather(b, n, m, _p(xyz), _p(temp), _p(idx),
-                                                               _p(new_xyz), _stream()), "fps_gather")
+        nbytes = lib.ws3d_fps_workspace_bytes(b, n)
+        if nbytes:          # 16384 < n <= 65536: the pruned kernels, as above
+            ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            check(lib.ws3d_furthest_point_sampling_ws(b, n, m, _p(xyz), _p(temp), _p(idx), _p(new_xyz), _p(ws), nbytes, _stream()), "fps_gather")
+        else:
+            check(lib.ws3d_furthest_point_sampling_gather(b, n, m, _p(xyz), _p(temp), _p(idx),
+                                                          _p(new_xyz), _stream()), "fps_gather")
     return 1
 
 

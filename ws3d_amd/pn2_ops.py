@@ -61,7 +61,11 @@ def _dense(**tensors):
 def furthest_point_sample_gather(xyz: torch.Tensor, npoint: int) -> Tuple[torch.Tensor, torch.Tensor]:
     """Fused FPS + gather: (idx (B,npoint) int32, new_xyz (B,npoint,3)).  new_xyz equals
     gather_operation(xyz^T, idx)^T bit for bit (pure copies).  No temp buffer is needed for
-    N <= 16384 (the running min-distance lives in registers)."""
+    N <= 16384 (the running min-distance lives in registers).  For 16384 < N <= 65536 the compat
+    wrapper allocates a scratch buffer (ws3d_fps_workspace_bytes: 20 bytes per point) and runs the
+    pruned kernels of csrc/fps_pruned.hip (same indices and centres, ties included;
+    WS3D_FPS_PRUNED=0 selects the streaming kernel); above 65536 points the streaming kernel works
+    in the temp buffer."""
     _dense(xyz=xyz)
     B, N, _ = xyz.size()
     idx = _new((B, npoint), torch.int32, xyz)
