@@ -801,6 +801,30 @@ WS3D_API int ws3d_stage2_select(int batch, int slots, float cls_thresh, float io
                                 const float *box_ce, const float *rcnn_ref, const float *rcnn_cls, const float *rcnn_iou, const float *center,
                                 const int32_t *num, float *boxes, int32_t *keep, float *key, ws3d_stream_t stream);
 
+/* Additive to ABI 6: no existing entry changed.  Stage 2 on WHOLE instance clouds of different sizes (csrc/stage2_ragged.hip), the form
+ * tools/eval_auto.py:286-403 evaluates in: cloud i owns the packed rows offsets[i] .. offsets[i+1]; offsets (clouds + 1) DEVICE int32,
+ * ascending, offsets[0] = 0; sizes_host (clouds) a HOST copy of the sizes, every one >= 1 (else WS3D_E_INVALID before any launch).
+ *
+ * ws3d_stage2_canonical_ragged: pts (rows, 5) = [x, y, z, reflectance, mask], box_ce (clouds, 7) -> pts_out (rows, 5): the canonical
+ * transform of ws3d_stage2_embed with the box of the row's OWN cloud (found by a search over offsets per row: nothing depends on clouds
+ * being aligned to tiles), same fp32 operations in the same order; reflectance and mask copied.  ws3d_stage2_embed(pts_out, NULL) is
+ * bit-equal to ws3d_stage2_embed(pts_i, box_i) on each cloud alone.  rows must equal offsets[clouds].                              */
+WS3D_API int ws3d_stage2_canonical_ragged(int rows, int clouds, const int32_t *offsets, const float *pts, const float *box_ce, float extend,
+                                          float *pts_out, ws3d_stream_t stream);
+/* ws3d_furthest_point_sampling_ragged that also writes new_xyz (clouds, m, 3) = xyz[offsets[i] + idx[i]] and accepts m > n_i: the result
+ * is then what sampling_gpu.cu:93-209 gives with block = opt_n_threads(n_i) -- once the distinct points are used up the running minima
+ * are all 0 and the tie rule returns index 0.  idx (clouds, m) local to each cloud, bit-equal to ws3d_furthest_point_sampling on cloud i
+ * alone for every n_i >= 1.  Clouds above ws3d_fps_ragged_limit() points are forwarded to ws3d_furthest_point_sampling_gather, one
+ * launch each on the same stream.                                                                                                    */
+WS3D_API int ws3d_furthest_point_sampling_ragged_gather(int clouds, const int32_t *offsets, const int32_t *sizes_host, int m, const float *xyz,
+                                                        int32_t *idx, float *new_xyz, ws3d_stream_t stream);
+/* ball_query_kernel_fast (ball_query_gpu.cu:9-45) per cloud: xyz (total, 3) packed, new_xyz (clouds, m, 3) -> idx (clouds, m, nsample):
+ * the cloud's points in ascending index, d2 < radius * radius strictly, the first hit fills all nsample slots, stop at nsample, a centre
+ * without a hit keeps 0.  global_rows = 1 adds offsets[i] to every entry (the padding zeros included), so the lists index the packed
+ * array.  nsample <= 64 (else WS3D_E_UNSUPPORTED).  Every element of idx is written; no atomics, allocation or host synchronisation.  */
+WS3D_API int ws3d_ball_query_ragged(int clouds, const int32_t *offsets, int m, float radius, int nsample, const float *xyz, const float *new_xyz,
+                                    int global_rows, int32_t *idx, ws3d_stream_t stream);
+
 /* The Stage-2 training losses (lib/net/train_functions.py:230-516, lib/utils/loss_utils.py:151-338 with LOC_XZ_FINE = LOC_Y_BY_BIN =
  * get_ry_fine = False), value AND gradient in one launch of one workgroup each: no host branch on fg_sum / iou_sum, no read-back, no
  * atomics, sums folded in a fixed order (a call is bit-reproducible).  Row terms in float64 from the fp32 inputs; the paired 3-D IoU

@@ -148,6 +148,9 @@ SIGNATURES = {
     "ws3d_stage2_embed": (_i, [C.c_long, _i, _vp, _vp, _f] + [_vp] * 10 + [_vp, _vp, _vp]),
     "ws3d_stage2_boxes": (_i, [_i, _i, _i, _f, _f, _f, _f, _vp, _vp, _vp, _vp]),
     "ws3d_stage2_select": (_i, [_i, _i, _f, _f, C.POINTER(_f), _f, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ws3d_stage2_canonical_ragged": (_i, [_i, _i, _vp, _vp, _vp, _f, _vp, _vp]),
+    "ws3d_furthest_point_sampling_ragged_gather": (_i, [_i, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "ws3d_ball_query_ragged": (_i, [_i, _vp, _i, _f, _i, _vp, _vp, _i, _vp, _vp]),
     "ws3d_stage2_rcnn_loss": (_i, [_i, _i, _i, _f, _f, _f, _f] + [_vp] * 9 + [_vp]),
     "ws3d_stage2_ioun_loss": (_i, [_i] + [_vp] * 10 + [_vp]),
     "ws3d_rpn_center_labels": (_i, [_i, _i, _i, _i, _f, _f, C.c_double] + [_vp] * 5 + [_vp]),

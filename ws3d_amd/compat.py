@@ -1647,6 +1647,73 @@ def stage2_boxes(rcnn_reg, loc_scope, loc_bin_size, num_head_bin, mean_size):
     return pred, ce
 
 
+def _ragged_sizes(what, offsets, sizes_host, rows):
+    """the checks every ragged Stage-2 entry shares -> (C, ctypes int32 array of the sizes)"""
+    import ctypes as _ct
+    _i32(offsets, "offsets")
+    C = len(sizes_host)
+    sizes = [int(s) for s in sizes_host]
+    if offsets.dim() != 1 or offsets.numel() != C + 1:
+        raise Ws3dError(f"{what}: offsets must be ({C + 1},), got {tuple(offsets.shape)}")
+    if any(s < 1 for s in sizes):
+        raise Ws3dError(f"{what}: every cloud must hold at least one point, sizes {sizes}")
+    if sum(sizes) != rows:
+        raise Ws3dError(f"{what}: the sizes add up to {sum(sizes)} rows, the packed array holds {rows}")
+    return C, (_ct.c_int32 * max(C, 1))(*sizes)
+
+
+def stage2_canonical_ragged(pts, offsets, sizes_host, box_ce, extend=1.2):
+    """pts (T,5) packed rows [x, y, z, reflectance, mask], offsets (C+1,) int32 on the device, sizes_host the C sizes, box_ce (C,7) ->
+    (T,5): every row in the frame of its own cloud's box (ws3d_stage2_canonical_ragged); stage2_embed of the result without a box is
+    bit-equal to stage2_embed of each cloud with its box"""
+    dev = _dev(pts, offsets, box_ce)
+    _f32(pts, "pts"); _f32(box_ce, "box_ce")
+    if pts.dim() != 2 or pts.size(1) != 5:
+        raise ValueError("stage2_canonical_ragged: pts must be (T,5), got %s" % (tuple(pts.shape),))
+    C, _ = _ragged_sizes("stage2_canonical_ragged", offsets, sizes_host, pts.size(0))
+    if tuple(box_ce.shape) != (C, 7):
+        raise ValueError("stage2_canonical_ragged: box_ce must be (%d,7), got %s" % (C, tuple(box_ce.shape)))
+    out = torch.empty_like(pts)
+    with _on(dev):
+        check(_lib.load().ws3d_stage2_canonical_ragged(pts.size(0), C, _p(offsets), _p(pts), _p(box_ce), float(extend), _p(out), _stream()),
+              "stage2_canonical_ragged")
+    return out
+
+
+def furthest_point_sampling_ragged_gather(xyz, offsets, sizes_host, m):
+    """xyz (T,3) packed, offsets (C+1,) int32 on the device, sizes_host the C sizes (each >= 1; m may exceed them) ->
+    (idx (C,m) int32 local to each cloud, new_xyz (C,m,3)) (ws3d_furthest_point_sampling_ragged_gather)"""
+    import ctypes as _ct
+    dev = _dev(xyz, offsets)
+    _f32(xyz, "xyz")
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise Ws3dError(f"fps_ragged_gather: xyz must be (T,3), got {tuple(xyz.shape)}")
+    C, sizes = _ragged_sizes("fps_ragged_gather", offsets, sizes_host, xyz.size(0))
+    idx = torch.empty((C, int(m)), dtype=torch.int32, device=dev)
+    new_xyz = torch.empty((C, int(m), 3), dtype=torch.float32, device=dev)
+    with _on(dev):
+        check(_lib.load().ws3d_furthest_point_sampling_ragged_gather(C, _p(offsets), _ct.cast(sizes, _ct.c_void_p), int(m), _p(xyz), _p(idx),
+                                                                     _p(new_xyz), _stream()), "fps_ragged_gather")
+    return idx, new_xyz
+
+
+def ball_query_ragged(radius, nsample, xyz, offsets, sizes_host, new_xyz, global_rows=False):
+    """xyz (T,3) packed, offsets (C+1,) int32 on the device, sizes_host the C sizes, new_xyz (C,m,3) -> idx (C,m,nsample) int32: the
+    reference's ball query per cloud; global_rows: the entries index the packed array (offsets[i] added) (ws3d_ball_query_ragged)"""
+    dev = _dev(xyz, offsets, new_xyz)
+    _f32(xyz, "xyz"); _f32(new_xyz, "new_xyz")
+    if xyz.dim() != 2 or xyz.size(1) != 3:
+        raise Ws3dError(f"ball_query_ragged: xyz must be (T,3), got {tuple(xyz.shape)}")
+    C, _ = _ragged_sizes("ball_query_ragged", offsets, sizes_host, xyz.size(0))
+    if new_xyz.dim() != 3 or new_xyz.size(0) != C or new_xyz.size(2) != 3:
+        raise Ws3dError(f"ball_query_ragged: new_xyz must be ({C},m,3), got {tuple(new_xyz.shape)}")
+    idx = torch.empty((C, new_xyz.size(1), int(nsample)), dtype=torch.int32, device=dev)
+    with _on(dev):
+        check(_lib.load().ws3d_ball_query_ragged(C, _p(offsets), new_xyz.size(1), float(radius), int(nsample), _p(xyz), _p(new_xyz),
+                                                 1 if global_rows else 0, _p(idx), _stream()), "ball_query_ragged")
+    return idx
+
+
 def stage2_select(box_ce, rcnn_ref, rcnn_cls, rcnn_iou, center, num, cls_thresh, iou_thresh, size_window, ground_y):
     """box_ce (B,K,7), rcnn_ref (B,K,7), rcnn_cls (B,K), rcnn_iou (B,K), center (B,K,3), num (B,) int32 -> (boxes (B,K,7) in the scene's
     frame, keep (B,K) int32, key (B,K): rcnn_iou where kept, -1e30 elsewhere) (ws3d_stage2_select)"""

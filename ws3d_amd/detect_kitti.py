@@ -20,6 +20,7 @@ import torch
 from . import kitti_io, scan_prepare, stage1, stage2
 
 OUT_KEYS = ("rcnn_cls", "rcnn_iou", "rcnn_ref", "box_ce")
+CLOUD_ROUTES = ("fixed", "ragged")
 
 
 def load_stage2(rcnn_ckpt=None, device="cuda:0", rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG, num_point: int = 512):
@@ -67,17 +68,62 @@ def rcnn_over_real_slots(s2, inp: dict, rcnn_batch: int = 800) -> dict:
 
 
 @torch.no_grad()
+def rcnn_over_real_clouds_ragged(s2, inp: dict, rcnn_batch: int = 800) -> dict:
+    """``Stage2Net.rcnn_forward_ragged`` over the WHOLE cylinders of a ``stage2_inputs(sampled_pt_num=None)`` dict (cur_box_point
+    (T,3), cur_box_reflect, train_mask, offsets (B K + 1), center (B,K,3), num (B)), as tools/eval_auto.py:286-403 feeds
+    them: the padding slots k >= num[b] and the empty cylinders (eval_auto.py:339 ``continue``s) are dropped, the others run in
+    chunks of at most min(rcnn_batch, 511) clouds -> the OUT_KEYS rows for all B K slots.  A dropped slot holds zeros, with rcnn_cls
+    and rcnn_iou at -inf: no threshold of ``stage2.detections`` keeps it.  One host read-back (the sizes)."""
+    center = inp["center"]
+    B, K = center.shape[0], center.shape[1]
+    host = torch.cat((inp["offsets"].reshape(-1).to(torch.int64), inp["num"].reshape(-1).to(torch.int64))).cpu().numpy()
+    start, num = host[:B * K + 1], host[B * K + 1:]
+    cnt = np.diff(start)
+    kept = [s for s in range(B * K) if s % K < num[s // K] and cnt[s] > 0]
+    widths = {"rcnn_cls": 1, "rcnn_iou": 1, "rcnn_ref": 7, "box_ce": 7}
+    full = {k: torch.zeros((B * K, w), dtype=torch.float32, device=center.device) for k, w in widths.items()}
+    dropped = torch.ones(B * K, dtype=torch.bool)
+    dropped[torch.as_tensor(kept, dtype=torch.int64)] = False
+    dropped = dropped.to(center.device)
+    for k in ("rcnn_cls", "rcnn_iou"):
+        full[k][dropped] = float("-inf")
+    step = max(1, min(int(rcnn_batch), stage2.RAGGED_MAX_CLOUDS))
+    for i0 in range(0, len(kept), step):
+        slots = kept[i0:i0 + step]
+        sizes = [int(cnt[s]) for s in slots]
+        r0, r1 = int(start[slots[0]]), int(start[slots[-1] + 1])
+        if r1 - r0 == sum(sizes):          # nothing but dropped (empty) slots in between: the chunk is one slice of the packed rows
+            rows = slice(r0, r1)
+        else:
+            rows = torch.from_numpy(np.concatenate([np.arange(start[s], start[s + 1]) for s in slots])).to(center.device)
+        sub = {k: inp[k][rows].contiguous() for k in ("cur_box_point", "cur_box_reflect", "train_mask")}
+        sub["offsets"] = torch.from_numpy(np.concatenate(([0], np.cumsum(sizes))).astype(np.int32)).to(center.device)
+        res = s2.rcnn_forward_ragged(sub, sizes=sizes)
+        sel = torch.as_tensor(slots, dtype=torch.int64, device=center.device)
+        for k in OUT_KEYS:
+            full[k][sel] = res[k].reshape(len(slots), -1)
+    return full
+
+
+@torch.no_grad()
 def detect_batch(s1, s2, pts: torch.Tensor, cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG,
-                 rcnn_batch: int = 800):
-    """pts (B,N,4) scenes -> (boxes (B,K,7), scores (B,K), count (B,)): K = the largest number of centres Stage 1 keeps in a scene"""
+                 rcnn_batch: int = 800, clouds: str = "fixed"):
+    """pts (B,N,4) scenes -> (boxes (B,K,7), scores (B,K), count (B,)): K = the largest number of centres Stage 1 keeps in a scene.
+    clouds: "fixed" -- every instance cloud brought to cfg.roi_sampled_pts rows (the reference's training format); "ragged" -- every
+    cylinder whole, whatever its size (the reference's evaluation, tools/eval_auto.py:286-403)"""
+    if clouds not in CLOUD_ROUTES:
+        raise ValueError("clouds must be one of %s, got %r" % (CLOUD_ROUTES, clouds))
     out = s1.rpn_forward({"pts_input": pts})
+    if clouds == "ragged":
+        inp = stage1.stage2_inputs(out, pts, cfg, sampled_pt_num=None, ground_y=rcnn_cfg.ground_y)
+        return stage2.detections(rcnn_over_real_clouds_ragged(s2, inp, rcnn_batch), inp["center"], inp["num"], rcnn_cfg)
     inp = stage1.stage2_inputs(out, pts, cfg, sampled_pt_num=cfg.roi_sampled_pts, ground_y=rcnn_cfg.ground_y)
     return stage2.detections(rcnn_over_real_slots(s2, inp, rcnn_batch), inp["center"], inp["num"], rcnn_cfg)
 
 
 def run(root: str, split: str, out_dir: str, batch: int = 4, ckpt: str | None = None, rcnn_ckpt: str | None = None, npoints: int = 16384,
         seed: int = 666, device: str = "cuda:0", cfg: stage1.RPNConfig = stage1.DEFAULT_CFG, rcnn_cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG,
-        rcnn_batch: int = 800, device_ingest: str = "off") -> list:
+        rcnn_batch: int = 800, device_ingest: str = "off", clouds: str = "fixed") -> list:
     """returns the list of result files written (one per scene, possibly empty)"""
     s1, s2 = load_models(ckpt, rcnn_ckpt, device, cfg, rcnn_cfg)
     scenes = kitti_io.KittiScenes(root, split, npoints=npoints, rng=np.random.RandomState(seed))     # eval_auto.py:139 seeds numpy with 666
@@ -87,7 +133,7 @@ def run(root: str, split: str, out_dir: str, batch: int = 4, ckpt: str | None = 
     for i0 in range(0, len(scenes), batch):
         items = [dataset[i] for i in range(i0, min(i0 + batch, len(scenes)))]
         pts = torch.as_tensor(scan_prepare.batch_points(items, device_ingest, npoints, seed, device)).to(torch.device(device))
-        boxes, scores, count = (t.cpu().numpy() for t in detect_batch(s1, s2, pts, cfg, rcnn_cfg, rcnn_batch))
+        boxes, scores, count = (t.cpu().numpy() for t in detect_batch(s1, s2, pts, cfg, rcnn_cfg, rcnn_batch, clouds))
         for j, item in enumerate(items):
             sid, k = int(item["sample_id"]), int(count[j])
             written.append(kitti_io.save_kitti_format(sid, scenes.get_calib(sid), boxes[j, :k], out_dir, scores[j, :k],
@@ -108,10 +154,13 @@ def main():
     ap.add_argument("--device_ingest", default="off", choices=scan_prepare.ROUTES,
                     help="off: the reference's host sampler (default); device: project, filter and sample the raw scans in one HIP call "
                          "(ws3d_amd.scan_prepare, another random stream); host: the same rows computed on the host")
+    ap.add_argument("--clouds", default="fixed", choices=CLOUD_ROUTES,
+                    help="fixed: every instance cloud cut or repeated to 512 rows (default); ragged: every cylinder whole, as the "
+                         "reference evaluates (Stage2Net.rcnn_forward_ragged)")
     ap.add_argument("--eval", action="store_true",
                     help="score the written files against root/training/label_2 and root/ImageSets/<split>.txt (ws3d_amd.kitti_eval)")
     a = ap.parse_args()
-    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.rcnn_ckpt, a.npoints, rcnn_batch=a.rcnn_batch, device_ingest=a.device_ingest)
+    files = run(a.root, a.split, a.out, a.batch, a.ckpt, a.rcnn_ckpt, a.npoints, rcnn_batch=a.rcnn_batch, device_ingest=a.device_ingest, clouds=a.clouds)
     print(f"{len(files)} result files in {a.out}")
     if a.eval:
         from . import kitti_eval

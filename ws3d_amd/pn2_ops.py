@@ -133,6 +133,39 @@ def furthest_point_sample_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoin
     return idx
 
 
+def _ragged_args(xyz, offsets, sizes):
+    if xyz.dim() != 2 or xyz.size(1) != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+        raise ValueError(f"xyz (T,3) and offsets (C+1,) expected, got {tuple(xyz.shape)} {tuple(offsets.shape)}")
+    if sizes is None:
+        sizes = (offsets[1:] - offsets[:-1]).tolist()      # (read back once: the entries validate the sizes on the host)
+    sizes = [int(s) for s in sizes]
+    if len(sizes) != offsets.numel() - 1 or any(s < 1 for s in sizes) or sum(sizes) != xyz.size(0):
+        raise ValueError(f"{offsets.numel() - 1} non-empty clouds that add up to {xyz.size(0)} rows expected, got sizes {sizes[:8]} ...")
+    _dense(xyz=xyz, offsets=offsets)
+    return offsets.to(torch.int32), sizes
+
+
+def furthest_point_sample_gather_ragged(xyz: torch.Tensor, offsets: torch.Tensor, npoint: int, sizes=None):
+    """``furthest_point_sample_ragged`` that also returns the sampled coordinates and accepts clouds SMALLER than npoint (the first
+    set-abstraction level of Stage 2 samples 128 centres out of a 37-point cylinder): -> idx (C,npoint) int32 local to each cloud,
+    new_xyz (C,npoint,3).  Row i equals ``furthest_point_sample(cloud_i[None], npoint)[0]`` bit for bit for every n_i >= 1; once a
+    cloud's distinct points are used up the reference's tie rule returns index 0.  sizes: the C sizes on the host, when the caller has
+    them (else offsets is read back once).  Device tensors only."""
+    offsets, sizes = _ragged_args(xyz, offsets, sizes)
+    with torch.no_grad():
+        return _C.furthest_point_sampling_ragged_gather(xyz, offsets, sizes, int(npoint))
+
+
+def ball_query_ragged(radius: float, nsample: int, xyz: torch.Tensor, offsets: torch.Tensor, new_xyz: torch.Tensor, sizes=None,
+                      global_rows: bool = False) -> torch.Tensor:
+    """``ball_query`` per cloud of a packed batch: xyz (T,3), offsets (C+1,), new_xyz (C,m,3) -> (C,m,nsample) int32; row i equals
+    ``ball_query(radius, nsample, cloud_i[None], new_xyz[i][None])[0]``.  global_rows: every entry (the zeros of the padding included)
+    gets offsets[i] added, so the lists index the packed array.  nsample <= 64.  Device tensors only."""
+    offsets, sizes = _ragged_args(xyz, offsets, sizes)
+    with torch.no_grad():
+        return _C.ball_query_ragged(radius, nsample, xyz, offsets, sizes, new_xyz.contiguous(), global_rows)
+
+
 def fps_ragged_limit() -> int:
     """the largest cloud the ragged kernel keeps on chip"""
     return _C.fps_ragged_limit()

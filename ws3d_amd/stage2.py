@@ -401,10 +401,11 @@ def _front_rows(model, pts5, box_ce, up_xyz, up_feat, merge):
     return xyz_out, feat.view(pts5.shape[0], pts5.shape[1], -1)
 
 
-def _tower_rows(xyz, feats, sa_modules, trace):
-    """the set-abstraction levels of a tower over channels-last rows -> (R, 512)"""
+def _tower_rows(xyz, feats, sa_modules, trace, first_level=0):
+    """the set-abstraction levels of a tower over channels-last rows -> (R, 512); first_level: the position of sa_modules[0] in the
+    tower (the ragged route runs level 0 itself and hands over the levels behind it)"""
     from . import compat as _C, fastpath as fp
-    for level, sa in enumerate(sa_modules):
+    for level, sa in enumerate(sa_modules, first_level):
         if sa.npoint is not None:
             new_xyz, new_feats = fp.sa_forward(sa, xyz, feats, level=level)
             _trace_level(trace, sa, xyz, new_xyz)
@@ -463,6 +464,108 @@ def fast_forward(model: RCNNNet, input_data, box_ce=None, trace=None, towers='bo
     return ret
 
 
+# --------------------------------------------------------------------------- the channels-last route on WHOLE clouds of different sizes
+RAGGED_MAX_CLOUDS = 511       # per call of the ragged route: the consumer kernels take rows // 64 <= 65535 (128 centres x 64 samples a cloud)
+
+
+def ragged_max_clouds(model: RCNNNet) -> int:
+    """the clouds one pass of the ragged route takes: level 1's C * npoint * nsample list entries / 64 must fit the consumer kernels'
+    16-bit grid, and never more than RAGGED_MAX_CLOUDS"""
+    sa = model.SA_modules[0]
+    return max(1, min(RAGGED_MAX_CLOUDS, (65535 * 64) // (sa.npoint * sa.groupers[0].nsample)))
+
+
+def _sa_level_ragged(sa, xyz, feats, offsets, sizes, trace):
+    """The first set-abstraction level over packed rows: xyz (T,3), feats (T,C), cloud i = rows offsets[i] .. offsets[i+1] ->
+    new_xyz (Cn,m,3), new_feats (Cn,m,O).  The geometry comes from csrc/stage2_ragged.hip (sampling with gather, ball query with
+    lists that index the packed array); the SharedMLP and the pool run through the consumer kernels of ``fastpath.sa_forward`` with
+    the packed batch as ONE scene of T points and Cn * m centres."""
+    from . import compat as _C, fastpath as fp, pn2_ops
+    g, blocks = sa.groupers[0], fp._blocks(sa.mlps[0])
+    Cn, T, m, ns = len(sizes), xyz.shape[0], sa.npoint, g.nsample
+    idx, new_xyz = pn2_ops.furthest_point_sample_gather_ragged(xyz, offsets, m, sizes=sizes)
+    nbr = pn2_ops.ball_query_ragged(g.radius, ns, xyz, offsets, new_xyz, sizes=sizes, global_rows=True)
+    if trace is not None:
+        trace.append({'new_xyz': new_xyz, 'fps': idx, 'bq': nbr - offsets[:-1].view(Cn, 1, 1)})
+    x1, c1, n1, f1 = xyz.view(1, T, 3), new_xyz.view(1, Cn * m, 3), nbr.view(1, Cn * m, ns), feats.view(1, T, -1)
+    wt1, b1, r1 = fp._row_weights_xyz_last(blocks[0])
+    o1 = blocks[0].conv.out_channels
+    y, rest = None, blocks[1:-1]
+    if len(blocks) >= 3:
+        # layer 1 is linear in the grouped row: its feature part is one product over the packed points, the lists gather it
+        pmat, offs, w1xs = fp._per_point_l1(sa, f1, [nbr])
+        if o1 <= 128:
+            wt2, b2, r2 = fp._row_weights(blocks[1])
+            y = _C.pgather_gemm2(pmat, offs[0], o1, x1, c1, n1, w1xs[0], b1, r1, wt2, b2, r2)
+            rest = blocks[2:-1]
+        if y is None:
+            y = _C.pgather_rows(pmat, offs[0], o1, x1, c1, n1, w1xs[0], b1, r1)
+            rest = blocks[1:-1]
+    if y is None:
+        y = _C.gather_gemm(f1, x1, c1, n1, wt1, b1, r1)
+        rest = blocks[1:-1]
+    if y is None:
+        raise RuntimeError("no consumer kernel took the ragged level (%d rows, %d -> %d channels)" % (n1.numel(), feats.shape[1], o1))
+    for blk in rest:
+        y = fp._layer(y, blk)
+    wt, bias, relu = fp._row_weights(blocks[-1])
+    out = torch.empty((Cn * m, wt.size(1)), dtype=torch.float32, device=xyz.device)
+    if not (fp.FUSED_GEMM_POOL and _C.gemm_pool(y, wt, bias, relu, ns, out, 0)):
+        _C.rowmax_rows(fp._layer(y, blocks[-1]), ns, out, 0)
+    return new_xyz, out.view(Cn, m, -1)
+
+
+@torch.no_grad()
+def fast_forward_ragged(model: RCNNNet, input_data, sizes, box_ce=None, trace=None, towers='both'):
+    """``fast_forward`` for Cn whole clouds of different sizes packed into (T,.) rows (``Stage2Net.rcnn_forward_ragged`` states the
+    inputs): the tower fronts per row, level 1 of each tower through ``_sa_level_ragged``, everything behind it on the fixed-size
+    (Cn, npoint, .) tensors as in ``fast_forward``.  At most ``ragged_max_clouds(model)`` clouds."""
+    from . import compat as _C
+    c = model.cfg
+    offsets = input_data['offsets'].to(torch.int32).contiguous()
+    pts5 = torch.cat((input_data['cur_box_point'], input_data['cur_box_reflect'], input_data['train_mask']), dim=-1).contiguous()
+    T, R = pts5.shape[0], len(sizes)
+
+    def tower(rows5, up_xyz, up_feat, merge, sa_modules):
+        x, f = _front_rows(model, rows5.view(1, T, 5), None, up_xyz, up_feat, merge)
+        nx, nf = _sa_level_ragged(sa_modules[0], x.view(T, 3), f.view(T, -1), offsets, sizes, trace)
+        return x.view(T, 3), _tower_rows(nx, nf, sa_modules[1:], trace, first_level=1)
+
+    _, top = tower(pts5, model.xyz_up_layer, model.feature_up_layer, model.merge_down_layer, model.SA_modules)
+    rcnn_cls, rcnn_reg = _head_rows(top, model.cls_layer), _head_rows(top, model.reg_layer)
+    if towers == 'rcnn':
+        decoded, _ = _C.stage2_boxes(rcnn_reg, c.loc_scope, c.loc_bin_size, c.num_head_bin, c.cls_mean_size)
+        ret = {'rcnn_cls': rcnn_cls, 'rcnn_reg': rcnn_reg, 'pred_boxes3d': decoded.view(R, 1, 7)}
+        ret.update(input_data)
+        return ret
+    if box_ce is not None:
+        pred_ce = box_ce.view(R, 7).contiguous()
+    else:
+        _, pred_ce = _C.stage2_boxes(rcnn_reg, c.loc_scope, c.loc_bin_size, c.num_head_bin, c.cls_mean_size)
+    can5 = _C.stage2_canonical_ragged(pts5, offsets, sizes, pred_ce, c.extend_factor)
+    xc, top = tower(can5, model.can_xyz_up_layer[0], model.can_feature_up_layer[0], model.can_merge_down_layer[0], model.SA_score_modules)
+    rcnn_iou, rcnn_ref, ioun_cls = _head_rows(top, model.IOU_layer[0]), _head_rows(top, model.ref_layer[0]), _head_rows(top, model.ICL_layer[0])
+    pred_boxes3d = center_box2box(pred_ce)
+    refined_box = refine_box(pred_boxes3d, rcnn_ref)
+    ret = {'rcnn_cls': rcnn_cls, 'rcnn_reg': rcnn_reg, 'rcnn_iou': rcnn_iou, 'rcnn_ref': rcnn_ref, 'ioun_cls': ioun_cls,
+           'pred_boxes3d': pred_boxes3d.view(R, 1, 7), 'refined_box': refined_box.view(R, 1, 7), 'box_ce': pred_ce, 'canonical_xyz': xc}
+    ret.update(input_data)
+    return ret
+
+
+RAGGED_KEYS = ('cur_box_point', 'cur_box_reflect', 'train_mask')
+
+
+def _cat_ragged(parts, input_data):
+    """the dicts of consecutive groups of clouds -> one: per-cloud rows concatenated, canonical_xyz as packed (T,3) rows"""
+    ret = {}
+    for k in parts[0]:
+        if k not in input_data:
+            ret[k] = torch.cat([p[k].reshape(-1, 3) if k == 'canonical_xyz' else p[k] for p in parts], dim=0)
+    ret.update(input_data)
+    return ret
+
+
 class Stage2Net(nn.Module):
     """``PointRCNN`` restricted to its Stage-2 half (lib/net/point_rcnn.py): attribute ``rcnn_net`` keeps the checkpoint prefix"""
 
@@ -504,6 +607,61 @@ class Stage2Net(nn.Module):
         return self.rcnn_net(input_data, towers=towers)
 
     forward = rcnn_forward
+
+    def rcnn_forward_ragged(self, input_data, towers='both', box_ce=None, trace=None, sizes=None):
+        """Stage 2 on WHOLE instance clouds, the form tools/eval_auto.py:286-403 evaluates in (every cylinder as it is, one cloud per
+        ``rcnn_forward`` call there).  input_data: cur_box_point (T,3), cur_box_reflect (T,1), train_mask (T,1) packed rows and
+        offsets (C+1): cloud i owns rows offsets[i] .. offsets[i+1] -- the slice of ``stage1.stage2_inputs(sampled_pt_num=None)`` for
+        the non-empty clouds.  sizes: the C sizes on the host when the caller has them (else offsets is read back once).
+        -> ``rcnn_forward``'s dict with R = C; canonical_xyz is (T,3).  box_ce (C,7) and trace as in ``RCNNNet.forward``; a trace
+        entry holds (C, npoint[, nsample]) tensors, indices local to each cloud.  An empty cloud raises ValueError.
+        An eval-mode model that ``supported`` accepts, on CUDA fp32 tensors with CHANNELS_LAST_FASTPATH set, takes
+        ``fast_forward_ragged`` (a few dozen launches per ``ragged_max_clouds`` clouds); everything else runs the reference's own form,
+        ``self.rcnn_net`` on (1, n_i, .) inputs cloud by cloud."""
+        xyz, offsets = input_data['cur_box_point'], input_data['offsets']
+        if towers not in ('both', 'rcnn'):
+            raise ValueError("towers must be 'both' or 'rcnn', got %r" % (towers,))
+        if xyz.dim() != 2 or xyz.shape[1] != 3 or offsets.dim() != 1 or offsets.numel() < 1:
+            raise ValueError("cur_box_point (T,3) and offsets (C+1,) expected, got %s %s" % (tuple(xyz.shape), tuple(offsets.shape)))
+        if sizes is None:
+            sizes = (offsets[1:] - offsets[:-1]).tolist()
+        sizes = [int(s) for s in sizes]
+        if len(sizes) != offsets.numel() - 1 or sum(sizes) != xyz.shape[0]:
+            raise ValueError("%d clouds that add up to %d rows expected, got sizes that add up to %d" % (offsets.numel() - 1, xyz.shape[0], sum(sizes)))
+        if any(s < 1 for s in sizes):
+            raise ValueError("cloud %d is empty: callers filter empty clouds out" % [i for i, s in enumerate(sizes) if s < 1][0])
+        net = self.rcnn_net
+        fast = (CHANNELS_LAST_FASTPATH and not net.training and xyz.is_cuda and xyz.dtype == torch.float32 and 'cur_pts_feature' not in input_data
+                and len(sizes) > 0)
+        if fast:
+            ok = net.__dict__.get("_fastpath_ok")
+            if ok is None:
+                ok = net.__dict__["_fastpath_ok"] = supported(net)
+            fast = ok
+        starts = np.concatenate(([0], np.cumsum(sizes))).astype(np.int64)
+        step = ragged_max_clouds(net) if fast else 1
+        parts, traces = [], []
+        for i0 in range(0, len(sizes), step):
+            i1 = min(i0 + step, len(sizes))
+            r0, r1 = int(starts[i0]), int(starts[i1])
+            tr = [] if trace is not None else None
+            ce = None if box_ce is None else box_ce[i0:i1]
+            if fast:
+                sub = {k: input_data[k][r0:r1] for k in RAGGED_KEYS}
+                sub['offsets'] = offsets if step >= len(sizes) else (offsets[i0:i1 + 1] - offsets[i0])
+                parts.append(fast_forward_ragged(net, sub, sizes[i0:i1], ce, tr, towers))
+            else:
+                sub = {k: input_data[k][r0:r1].unsqueeze(0) for k in RAGGED_KEYS}
+                parts.append(net(sub, box_ce=ce, trace=tr, towers=towers))
+            traces.append(tr)
+            for k in RAGGED_KEYS + ('offsets',):
+                parts[-1].pop(k, None)
+        if not parts:
+            raise ValueError("no cloud")
+        if trace is not None:
+            for lvl in range(len(traces[0])):
+                trace.append({k: torch.cat([t[lvl][k] for t in traces], dim=0) for k in traces[0][lvl]})
+        return _cat_ragged(parts, input_data)
 
 
 # --------------------------------------------------------------------------- the detection tail
