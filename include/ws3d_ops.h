@@ -896,6 +896,26 @@ WS3D_API int ws3d_scan_prepare(int scenes, const int32_t *offsets, long total_po
                                float *pts_input, int32_t *src_index, int32_t *valid_count, int32_t *status, void *workspace,
                                size_t workspace_bytes, ws3d_stream_t stream);
 
+/* Additive to ABI 6: no existing entry changed.  Stage-2 training batches from box records that lie on the device
+ * (csrc/stage2_batch.hip): what train_rcnn.BoxDataset.sample -> collate -> prepare_batch do per cloud on the host, for a batch in ONE
+ * launch with one workgroup per sample and no read-back.  ANOTHER random stream than BoxDataset's for the per-point draws (mask
+ * flips and shuffle: a counter-based hash of (sample_seed, row number)); every floating-point draw is made by the caller.  DESIGN.md
+ * 5.13a "Stage-2 batches on the device" states the contract, ws3d_amd/stage2_batch.py restates it bit for bit and builds the blocks.
+ *   params (samples) blocks of ws3d_stage2_batch_param_bytes() bytes each, on the device, 8-byte aligned:
+ *     double gt0, gt2 (the box centre the region drop-out compares x and z with), cx, cz (recentring offsets);
+ *     uint64 sample_seed; int32 record, flags, cut, pad; float revive_matrix[0] (16), revive_matrix[1] (16), Rot_y (16),
+ *     ext_noise (3), noise_scale.  flags: 1 TRAIN mode, 2 drop-out on, 4 / 8 its x / z side is '>', 16 OR of the sides (else AND),
+ *     32 rows with prob < 0 are kept as well, 64 x flip.  cut: the rows kept of a cloud that fills all 512 (512, 128 or 32).
+ *   rows (total_rows, 6) = [x, y, z, reflect, prob -+ 0.5, gt_mask - 0.5], 8-byte aligned; offsets (records + 1) int32: record r
+ *   holds the rows offsets[r] .. offsets[r+1]; key_bits 1..32 (32 in production; fewer bits force ties in the shuffle keys) ->
+ *   cur_box_point (samples, 512, 3), cur_box_reflect (samples, 512), train_mask (samples, 512); status (samples) or NULL: 0 ok,
+ *   3 a record index or offsets that do not describe a non-empty slice of rows -- such a sample's outputs are not touched.
+ * WS3D_E_INVALID: a negative count, total_rows above 2^31 - 1, key_bits out of range, a null or misaligned pointer; nothing launched. */
+WS3D_API int ws3d_stage2_batch_param_bytes(void);
+WS3D_API int ws3d_stage2_batch(int samples, const void *params, const float *rows, const int32_t *offsets, int records, long total_rows,
+                               int key_bits, float *cur_box_point, float *cur_box_reflect, float *train_mask, int32_t *status,
+                               ws3d_stream_t stream);
+
 /* ------------------------------------------------- test hooks */
 
 /* What ws3d_roipool3d / _fill / _ws would launch for these sizes under this process's WS3D_ROI_* knobs, without launching it:

@@ -159,6 +159,8 @@ SIGNATURES = {
     "ws3d_scan_prepare_limit": (_i, []),
     "ws3d_scan_prepare_workspace_bytes": (_sz, [_i, C.c_long]),
     "ws3d_scan_prepare": (_i, [_i, _vp, C.c_long, _i, _vp, _vp, _vp, _vp, _i, C.c_uint64, _vp, _i, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ws3d_stage2_batch_param_bytes": (_i, []),
+    "ws3d_stage2_batch": (_i, [_i, _vp, _vp, _vp, _i, C.c_long, _i, _vp, _vp, _vp, _vp, _vp]),
     "ws3d_roipool3d_plan": (_i, [_i, _i, _i, _i, _i, _i, _sz]),
     "ws3d_ball_query_plan": (_i, [_i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
 }

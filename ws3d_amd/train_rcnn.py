@@ -3,7 +3,7 @@
     python -m ws3d_amd.train_rcnn --data DIR/train_boxes.pkl | --synthetic N
                                   --phase rcnn|ioun [--batch_size 800] [--total_iters 40000]
                                   [--output_dir D] [--ckpt x.pth] [--pretrain_ckpt y.pth]
-                                  [--ckpt_save_interval 20] [--seed S] [--workers W]
+                                  [--ckpt_save_interval 20] [--seed S] [--workers W] [--device_batches off|device|host]
 
 Counterpart of tools/train_cascade1.py (``get_rcnn_loss``) and tools/train_cascade_later.py (``get_ioun_loss``) on what
 ``gen_box_dataset`` writes:
@@ -22,6 +22,10 @@ Counterpart of tools/train_cascade1.py (``get_rcnn_loss``) and tools/train_casca
     backward, ``clip_grad_norm_(1.0)``, Adam one-cycle with ``pct_start = 0.2`` (weaklyRCNN.yaml / weaklyIOUN.yaml; no BatchNorm, so
     no BN momentum schedule).  One host read per step, at its end.
   * ``SyntheticBoxes`` builds the same records from ``synth.roi_clouds`` with a known box per cloud, about half of them foreground.
+
+  * ``--device_batches device`` (opt-in) takes the batches from ``stage2_batch``: the records uploaded once, one HIP launch per batch
+    in place of ``BoxDataset.sample`` x batch, ``collate`` and ``prepare_batch``; ``host`` is its bit-exact numpy twin.  Same batch
+    composition and sample seeds as ever, another random stream for the per-point flips and the shuffle.
 
 Not here: the reference's per-20-iteration eval loop, TensorBoard, ``nn.DataParallel``, ``cur_pts_feature`` datasets.
 """
@@ -256,15 +260,16 @@ def prepare_batch(batch: dict, device=None, dtype=torch.float32) -> dict:
 
 # ----------------------------------------------------------------------------- training
 def train_step(model: stage2.Stage2Net, optimizer: AdamOneCycle, batch: dict, it: int, phase: str,
-               train_cfg: TrainConfig = STAGE2_TRAIN, device=None) -> dict:
+               train_cfg: TrainConfig = STAGE2_TRAIN, device=None, prepared: bool = False) -> dict:
     """one iteration: schedule, forward (``towers`` by phase), the phase's loss, backward, gradient clipping, optimizer step.
+    prepared: `batch` is what ``prepare_batch`` returns already (``stage2_batch.prepared_batches``), on the model's device.
     -> the step's tb_dict as floats (+ loss, grad_norm, lr), read back in ONE host synchronisation at the end"""
     assert phase in ("rcnn", "ioun")
     optimizer.schedule(it)
     if not model.training:
         model.train()
     optimizer.zero_grad()
-    data = prepare_batch(batch, device if device is not None else next(model.parameters()).device)
+    data = batch if prepared else prepare_batch(batch, device if device is not None else next(model.parameters()).device)
     inputs = {k: data[k] for k in ("cur_box_point", "cur_box_reflect", "train_mask") + IOU_KEYS if k in data}
     if phase == "rcnn":
         out = model.rcnn_forward(inputs, towers="rcnn")
@@ -303,8 +308,11 @@ def trained_parameters(model: stage2.Stage2Net, phase: str):
 
 def train(dataset: BoxDataset, phase: str, total_iters: int, batch_size: int = 800, output_dir: Optional[str] = None, ckpt: Optional[str] = None,
           pretrain_ckpt: Optional[str] = None, ckpt_save_interval: int = 20, seed: int = 0, workers: int = 0, device: str = "cuda:0",
-          cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG, train_cfg: TrainConfig = STAGE2_TRAIN, log=print):
-    """-> (model, history: the tb_dict of every step)"""
+          cfg: stage2.RCNNConfig = stage2.DEFAULT_CFG, train_cfg: TrainConfig = STAGE2_TRAIN, log=print, device_batches: str = "off"):
+    """-> (model, history: the tb_dict of every step).  device_batches: 'off' -- ``batches`` + ``prepare_batch`` as ever; 'device' / 'host'
+    -- prepared batches from ``stage2_batch`` (the kernel / its numpy twin; `workers` is not used)"""
+    if device_batches not in ("off", "device", "host"):
+        raise ValueError(f"device_batches must be one of off, device, host; got {device_batches!r}")
     torch.manual_seed(seed)
     dev = torch.device(device)
     model = build_model(phase, dev, cfg, pretrain_ckpt)
@@ -316,11 +324,15 @@ def train(dataset: BoxDataset, phase: str, total_iters: int, batch_size: int = 8
     if ckpt_dir:
         os.makedirs(ckpt_dir, exist_ok=True)
     history = []
-    stream = batches(dataset, batch_size, workers)
+    if device_batches == "off":
+        stream = batches(dataset, batch_size, workers)
+    else:
+        from . import stage2_batch
+        stream = stage2_batch.prepared_batches(dataset, batch_size, device_batches, dev)
     try:
         while it < total_iters:
             t0 = time.time()
-            tb = train_step(model, optimizer, next(stream), it, phase, train_cfg, dev)
+            tb = train_step(model, optimizer, next(stream), it, phase, train_cfg, dev, prepared=device_batches != "off")
             it += 1
             history.append(tb)
             main_key = "rcnn_loss" if phase == "rcnn" else "rcnn_loss_iou"
@@ -348,13 +360,17 @@ def main():
     ap.add_argument("--pretrain_ckpt", default=None, help="weights only (phase ioun: the phase-1 checkpoint)")
     ap.add_argument("--ckpt_save_interval", type=int, default=20)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--workers", type=int, default=0)
+    ap.add_argument("--workers", type=int, default=0, help="threads that prepare samples on the host; ignored with --device_batches device")
+    ap.add_argument("--device_batches", choices=("off", "device", "host"), default="off",
+                    help="device: the records live on the GPU and one HIP launch prepares a batch (stage2_batch); host: its bit-exact "
+                         "numpy twin (the route of a CPU device); off: BoxDataset + prepare_batch as ever")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     source = SyntheticBoxes(a.synthetic, a.seed) if a.synthetic is not None else a.data
     dataset = BoxDataset(source, "TRAIN", a.seed, a.phase, cascade=stage2.DEFAULT_CFG.cascade)
     print("%d records -> %d samples per epoch, phase %s" % (len(dataset) // AUG_NUM, len(dataset), a.phase))
-    train(dataset, a.phase, a.total_iters, a.batch_size, a.output_dir, a.ckpt, a.pretrain_ckpt, a.ckpt_save_interval, a.seed, a.workers, a.device)
+    train(dataset, a.phase, a.total_iters, a.batch_size, a.output_dir, a.ckpt, a.pretrain_ckpt, a.ckpt_save_interval, a.seed, a.workers, a.device,
+          device_batches=a.device_batches)
 
 
 if __name__ == "__main__":
